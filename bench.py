@@ -1,8 +1,22 @@
 """bench.py — PCG iterations/s on the north-star workload (BASELINE.json).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--n 65536] [--k 256]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run does what its headline figure needs and no more: it sets the problem up, runs W
+warm-up and K timed PCG iterations, writes the outputs of the timed path (--dump-outputs)
+and prints the JSON line.  --full adds the other legs to the same line: the solve to relres
+1e-6 with its comparison against the CPU oracle's committed solve, the CPU baseline, the
+N = 8192 parity run and the configs[3] size leg (cpu_baseline, solve_to_1e-6, parity_n8192,
+time_to_solution and configs3_leg are null / absent without it).
+
+--dump-outputs DIR writes what a caller of the timed path receives after the last timed
+iteration as float64 .npy files: DIR/x.npy (the iterate x_{W+K}, this rank's rows) and
+DIR/residual_trace.npy (the stop-test residual norms ||r_0|| .. ||r_{W+K}||); with several
+ranks rank r writes DIR/x_rank<r>.npy and rank 0 the trace.  The inputs are seeded, so two
+builds run with the same arguments can be compared array for array.
 
 With --gpus N > 1 and no WORLD_SIZE in the environment (the plain first form), the script
 launches its own N ranks: the parent process -- before it imports the library or touches a
@@ -27,9 +41,9 @@ iteration (the fp64 mat-vec over the whole N x N matrix + preconditioner apply +
 updates); with several GPUs the rows are sharded and the iteration runs three RCCL
 collectives (allgather of z, reduce-scatter of the partial K p, allreduce of ||r||^2 | T r).
 
-Prints the JSON line (rank 0) with the driver's keys -- once right after the configs[2] leg,
-and once more, identical plus `configs3_leg`, after the configs[3] leg (the last line is the
-complete one) -- with
+Prints the JSON line (rank 0) with the driver's keys -- with --full once right after the
+configs[2] leg, and once more, identical plus `configs3_leg`, after the configs[3] leg (the
+last line is the complete one) -- with
   roofline:     algorithmic bytes/launch of the K mat-vec / its mean HIP-event
                 duration, against 8 TB/s; traffic from profiles/ (PMC) or null.  With
                 the symmetric tiled storage (default) the bytes are the stored lower
@@ -37,9 +51,9 @@ complete one) -- with
                 matvec_gbs_dense_equivalent restates the rate against 8 N^2
   cpu_baseline: the NumPy/SciPy oracle (oracle/, a port of the reference's CPU
                 path) timed on this host on a bounded number of PCG iterations
-                of the same matrix (rank 0, N = 1 only)
+                of the same matrix (--full; rank 0, N = 1 only)
   parity:       iterations to relres 1e-6 on GPU vs the CPU oracle on an N = 8192
-                instance of the same generator (rank 0, N = 1 only)
+                instance of the same generator (--full; rank 0, N = 1 only)
 """
 from __future__ import annotations
 
@@ -92,6 +106,14 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: the solve to 1e-6 and "
+                         "its CPU-oracle comparison, the CPU baseline, the N = 8192 parity run, "
+                         "the configs[3] size leg (--no-cpu / --no-solve / --configs3-n 0 drop "
+                         "single legs of it)")
+    ap.add_argument("--dump-outputs", type=Path, default=None, metavar="DIR",
+                    help="write the outputs of the timed path after its last step (the iterate "
+                         "and the residual trace) as float64 DIR/<name>.npy")
     ap.add_argument("--n", type=int, default=None,
                     help="kernel size of `value` (default 65536 = configs[2], on any number "
                          "of GPUs)")
@@ -99,12 +121,13 @@ def parse():
                     help="preconditioner rank (rbf: 256; sGDML: the rule of thumb, e.g. 2701 "
                          "for the nanotube; configs[4] uses 1024)")
     ap.add_argument("--configs3-n", type=int, default=131072,
-                    help="rbf workload: also time this size (configs[3], N = 131072) on the "
-                         "same ranks (configs3_leg); 0 skips it")
+                    help="--full, rbf workload: also time this size (configs[3], N = 131072) on "
+                         "the same ranks (configs3_leg); 0 skips it")
     ap.add_argument("--lam", type=float, default=1e-6)
     ap.add_argument("--ell", type=float, default=0.2)
-    ap.add_argument("--no-cpu", action="store_true", help="skip the CPU baseline leg")
-    ap.add_argument("--no-solve", action="store_true", help="skip the solve-to-1e-6 legs")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline leg")
+    ap.add_argument("--no-solve", action="store_true",
+                    help="--full: skip the solve-to-1e-6 legs")
     ap.add_argument("--cpu-iters", type=int, default=30,
                     help="PCG iterations per CPU-baseline sample (3 samples, median; ~5 s each "
                          "at N=65536 on 16 cores)")
@@ -620,8 +643,8 @@ def sgdml_workload(args, rank, world, local, pg):
     _, t_chol = solver.precon_pivchol(k)
     # the first build includes one-time costs (code-object loads of its kernels, the scratch
     # arena's first chunks); a second, identical build shows the steady-state cost (skipped
-    # where the build itself takes seconds)
-    t_warm = solver.precon_pivchol(k)[1] if t_chol < 1.0 else None
+    # where the build itself takes seconds; a --full leg)
+    t_warm = solver.precon_pivchol(k)[1] if args.full and t_chol < 1.0 else None
     return solver, n, k, y, {"operator_setup_s": t_asm, "pivchol_build_s": t_chol,
                              "pivchol_build_warm_s": t_warm,
                              "assembled": args.storage in ("sym", "dense"),
@@ -755,10 +778,26 @@ def solo_profile(args):
         s.close()
 
 
+def dump_outputs(out_dir: Path, solver, rank: int, world: int) -> None:
+    """--dump-outputs: what a caller of the timed path holds after its last iteration, as
+    float64 .npy files -- this rank's rows of the iterate (pcg_x) and, on rank 0, the
+    stop-test residual norms of every iteration so far (pcg_trace).  N and W + K + 1 doubles:
+    0.5 MB at the configs[2] size, 4 MB at the largest published point (N = 505050)."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    np.save(out_dir / ("x.npy" if world == 1 else f"x_rank{rank}.npy"),
+            np.asarray(solver.pcg_x(), dtype=np.float64))
+    if rank == 0:
+        np.save(out_dir / "residual_trace.npy", np.asarray(solver.pcg_trace(), dtype=np.float64))
+
+
 def main():
     args = parse()
     if args.solo_world > 1:
         return solo_profile(args)
+    if not args.full:
+        # a plain run: set-up, warm-up, the timed steps, the result line
+        args.no_cpu = args.no_solve = True
+        args.configs3_n = 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `bench.py --gpus N`: launch the N ranks here (nothing has touched a GPU yet)
         sys.exit(launch_ranks(spawn_plan(sys.argv[1:], args.gpus, free_port(), os.environ),
@@ -810,6 +849,12 @@ def main():
     el = time.perf_counter() - t0
     el = max_over_ranks(pg, el)
     tm = solver.timing_read()
+    steps_run = solver.pcg_result()[0] - args.warmup
+    if steps_run != args.steps:
+        raise SystemExit(f"bench.py: the timed region ran {steps_run} PCG iterations, "
+                         f"--steps asked for {args.steps}")
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, solver, rank, world)
     gemv_ms = tm["gemv_ms"] / max(tm["gemv_count"], 1)
     iter_ms = tm["iter_ms"] / max(tm["iter_count"], 1)
     comm = None
@@ -966,6 +1011,7 @@ def main():
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
+            "full": bool(args.full),
             "ms_per_step": el / args.steps * 1e3,
             "higher_is_better": True,
             "scaling": "strong",

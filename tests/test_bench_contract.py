@@ -20,10 +20,35 @@ def test_defaults_are_the_driver_contract(monkeypatch):
     assert (a.gpus, a.steps, a.warmup) == (1, 50, 5)
     assert a.n is None and a.k is None          # -> N = 65536, k = 256 in main()
     assert a.workload == "rbf" and a.storage == "auto"
-    assert a.configs3_n == 131072               # the configs[3] leg rides along on every N
+    assert a.configs3_n == 131072               # the configs[3] leg of --full, on every N
+    assert a.full is False and a.dump_outputs is None   # a plain run: the headline figure only
     a = _args(monkeypatch, "--gpus", "8", "--steps", "20", "--warmup", "5")
     assert (a.gpus, a.steps, a.warmup) == (8, 20, 5)
     assert a.n is None                          # value stays the configs[2] problem at N > 1
+    a = _args(monkeypatch, "--full", "--dump-outputs", "some/dir")
+    assert a.full is True and a.dump_outputs == bench.Path("some/dir")
+    assert not (a.no_cpu or a.no_solve)         # --full runs every leg unless one is dropped
+
+
+def test_dump_outputs_writes_float64_arrays(tmp_path):
+    """--dump-outputs: x.npy (x_rank<r>.npy with several ranks) and, on rank 0,
+    residual_trace.npy, float64, in a directory the bench creates."""
+    import numpy as np
+
+    class Solver:
+        def pcg_x(self):
+            return np.arange(5, dtype=np.float64)
+
+        def pcg_trace(self):
+            return np.array([3.0, 2.0, 1.0])
+
+    bench.dump_outputs(tmp_path / "a" / "b", Solver(), 0, 1)
+    assert sorted(p.name for p in (tmp_path / "a" / "b").iterdir()) == ["residual_trace.npy", "x.npy"]
+    x = np.load(tmp_path / "a" / "b" / "x.npy")
+    assert x.dtype == np.float64 and np.array_equal(x, np.arange(5.0))
+    assert np.array_equal(np.load(tmp_path / "a" / "b" / "residual_trace.npy"), [3.0, 2.0, 1.0])
+    bench.dump_outputs(tmp_path / "c", Solver(), 1, 2)
+    assert [p.name for p in (tmp_path / "c").iterdir()] == ["x_rank1.npy"]
 
 
 def test_metric_matches_baseline():
