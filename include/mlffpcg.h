@@ -242,7 +242,13 @@ int mlff_matvec(mlff_ctx *ctx, const double *v_global, double *y_local);
  * preconditioner builds read the dense rows). */
 int mlff_set_storage(mlff_ctx *ctx, int mode);
 /* resolves the storage (building the tiles if needed) and reports the mode in
- * use and the algorithmic HBM bytes of one operator application on this rank */
+ * use and the algorithmic HBM bytes of one operator application on this rank:
+ * the bytes that are streamed.  Symmetric tiles generated from RBF points
+ * (mlff_gen_rbf, d <= 3) are in part evaluated again from the points instead of
+ * read (MLFF_SYM_GEN=0 turns that off): then 8 * 512^2 * (streamed whole tiles
+ * + the tiles run as quarter units) + 16 * rows.  The quarter units go to
+ * whichever role is free first and count as streamed, so the figure is an upper
+ * bound by less than one quarter tile per resident workgroup. */
 int mlff_storage_info(mlff_ctx *ctx, int *mode_out, double *bytes_per_matvec_out);
 /* form of the matrix-free sGDML operator (MLFF_STORAGE_MATFREE; the reference's K_op,
  * iterative_solver.py:383-445 / predict.py:172-220, evaluated three ways):

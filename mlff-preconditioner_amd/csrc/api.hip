@@ -301,6 +301,8 @@ int dev_free(void *p) {
 void rbf_free(mlff_ctx *ctx) {
   dev_free(ctx->rbf.Xs);
   ctx->rbf = RbfData();
+  ctx->sym.gen = false;  // tiles generated from these points stay valid, but are only streamed
+  ctx->sym.gsrc = SymGen{};
 }
 
 // the dense rows of the RBF source, generated on first use (DENSE storage, the masked
@@ -852,8 +854,17 @@ namespace {
 
 double operator_bytes(const mlff_ctx *ctx) {
   if (ctx->use_mf) return mf_bytes(ctx);
-  if (ctx->use_sym)
-    return 8.0 * (double)ctx->sym.ntiles * kSymTile * kSymTile + 16.0 * (double)ctx->nrows;
+  if (ctx->use_sym) {
+    // tiles streamed: all of them, or -- with a generating role (SymPack::gen) -- the whole
+    // tiles [0, n_s) and the quarter units unless all of those are generated; quarter units
+    // shared by the two roles count as streamed (an upper bound, by less than the resident
+    // workgroups' worth of quarter tiles)
+    const SymPack &sp = ctx->sym;
+    double tiles = (double)sp.ntiles;
+    if (sp.gen)
+      tiles = (double)sp.gsrc.n_s + (sp.gsrc.qmode == 2 ? 0.0 : (double)(sp.ntiles - sp.nwhole));
+    return 8.0 * tiles * kSymTile * kSymTile + 16.0 * (double)ctx->nrows;
+  }
   return 8.0 * (double)ctx->nrows * (double)ctx->N + 16.0 * (double)ctx->nrows;
 }
 

@@ -45,6 +45,26 @@ struct DevState {
   double rho_new;      // fused p update: rho of the iteration, published by k_rec_g for k_rec_fin
 };
 
+// Generating role of the tile mat-vec (kernels_sym.hip k_symv_dyn): where the tiles were
+// generated from the RBF points (k_sym_gen_rbf's inputs, resident in RbfData), part of the
+// workgroups evaluate their tiles' entries from the points -- the stored bits -- instead of
+// streaming them, on the fp64 pipe the stream leaves idle.
+constexpr int kSymGenMaxD = 3;  // point dimensions the role keeps in registers (above: all streamed)
+// whole tiles per ms of the two roles running side by side on one MI355X, one streaming and
+// one generating workgroup per CU, d = 3 (DESIGN.md 3.1 has the sweep they come from): the
+// static share is n_s = nwhole R_s / (R_s + R_g).  The same style of modelled rates as the
+// storage choice of resolve_storage (api.hip).
+constexpr double kSymStreamRate = 2550.0;
+constexpr double kSymGenRate = 2060.0;
+struct SymGen {
+  const double *Xs = nullptr;
+  int d = 0;
+  double jitter = 0.0;
+  int64_t N = 0, rows_per = 0, blk = 0;
+  int n_s = 0;    // whole tiles [0, n_s) are streamed, [n_s, nwhole) generated
+  int qmode = 0;  // quarter units: 0 either role, 1 all streamed, 2 all generated
+};
+
 // Lower-block-triangle tiles of K owned by this rank (kernels_sym.hip).
 struct SymPack {
   bool ready = false;
@@ -71,7 +91,9 @@ struct SymPack {
   int pmax = 0;
   int64_t t_split = 0;             // smallest I of a split tile (nb if none)
   int64_t dyn = 0;                 // > 0: k_symv_dyn with this many workgroups
-  unsigned long long *ticket = nullptr;  // its work counter (reset by the slot reduction)
+  unsigned long long *ticket = nullptr;  // its work counters (reset by the slot reduction)
+  bool gen = false;                // k_symv_dyn with a generating role (RBF source, sym_build)
+  SymGen gsrc;                     // its source and the share of the two roles
   double *yg = nullptr;      // world > 1: this rank's partial y, rank blocks of ystride
   double *yr = nullptr;      // world > 1: reduce-scatter result (ystride)
   int64_t ystride = 0;       // blk + tail (p.q shares of every rank)
@@ -137,19 +159,25 @@ struct RbfData {
   double jitter = 0.0;
 };
 
-// K[i, g] (i != g) of the sklearn RBF kernel: exp(-0.5 * sum_t (xs_i - xs_g)^2), the
-// squared distance formed without FMA contraction (scipy pdist 'sqeuclidean' order).
+// K[i, g] (i != g) of the sklearn RBF kernel: exp(-0.5 * sum_t (xs_i - xs_g)^2).  The squared
+// distance is the first square as a product and every further square through one fma --
+// d0 d0, fma(d1, d1, .), fma(d2, d2, .), ... -- written out so that every site that evaluates
+// an entry (the dense rows, the columns, the stored tiles and the tile mat-vec's generating
+// role) rounds alike whatever the optimiser does where it is inlined.  (The separate
+// multiply and add this replaced were contracted to exactly this by the compiler at every
+// site, so no stored value changed; scipy's pdist 'sqeuclidean' rounds each product.)
 // (xs_i - xs_g)^2 == (xs_g - xs_i)^2 exactly, so the generated kernel is exactly symmetric.
+__device__ __forceinline__ double rbf_sqdist_step(double s, double df, bool first) {
+  return first ? __dmul_rn(df, df) : fma(df, df, s);
+}
+__device__ __forceinline__ double rbf_of_sqdist(double s) { return exp(-0.5 * s); }
 __device__ __forceinline__ double rbf_value(const double (&xi)[8], const double *__restrict__ Xs,
                                             int64_t g, int d) {
   double s = 0.0;
 #pragma unroll
   for (int t = 0; t < 8; ++t)
-    if (t < d) {
-      const double df = __dsub_rn(xi[t], Xs[g * d + t]);
-      s = __dadd_rn(s, __dmul_rn(df, df));
-    }
-  return exp(-0.5 * s);
+    if (t < d) s = rbf_sqdist_step(s, __dsub_rn(xi[t], Xs[g * d + t]), t == 0);
+  return rbf_of_sqdist(s);
 }
 
 // The scipy stop test of iteration `it` (k_stoptest), done by every workgroup of the

@@ -15,7 +15,7 @@ __device__ __forceinline__ int64_t col_pos(int64_t g, int64_t rows_per, int64_t 
 
 // ---------------------------------------------------------------------------
 // K[i, pos(g)] = exp(-0.5 * sum_d (xs_i - xs_g)^2), diag = 1 + jitter.  The squared
-// distance is formed without FMA contraction (scipy pdist 'sqeuclidean' order).
+// distance is rounded as rbf_value (common.h) writes it: one product, then one fma per term.
 __global__ __launch_bounds__(256) void k_gen_rbf(double *__restrict__ K, int64_t ld,
                                                  int64_t nrows, int64_t row0, int64_t rows_per,
                                                  int64_t blk, int64_t N,

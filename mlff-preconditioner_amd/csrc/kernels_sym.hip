@@ -23,6 +23,11 @@
 // Every (slot, row) of the slot buffer P (nb x Np) is written by exactly one tile
 // (no atomics), and a second kernel sums the nb slots of each row in a fixed
 // order -> the result is bitwise deterministic.
+//
+// Tiles that were generated from the RBF points (k_sym_gen_rbf) need not all be read
+// again: in k_symv_dyn<true> half of the resident workgroups evaluate the entries of their
+// tiles from the points (the stored bits) on the fp64 pipe that the stream leaves idle,
+// while the other half streams.
 #include "common.h"
 
 #include <algorithm>
@@ -125,6 +130,7 @@ __device__ __forceinline__ void tile_body(const double *__restrict__ A, int I, i
   }
 }
 
+
 constexpr int kBatches = B / kRB;  // 8-row batches per tile
 
 // workgroups [0, nwhole): one whole tile each; then 2^lsub workgroups per remaining tile,
@@ -226,90 +232,205 @@ __device__ __forceinline__ d2 pg_val2(const PGather &pg, const double *v, int64_
   return d2{fma(beta, po.x, z.x), fma(beta, po.y, z.y)};
 }
 
-__global__ __launch_bounds__(256) void k_symv_dyn(const double *__restrict__ tiles,
-                                                  const int2 *__restrict__ list,
-                                                  const double *__restrict__ v,
-                                                  double *__restrict__ P,
-                                                  double *__restrict__ Pq, int64_t Np,
-                                                  int nwhole, long long nunits, int nb,
-                                                  int lsub,
-                                                  unsigned long long *__restrict__ ticket,
-                                                  const int *__restrict__ status, PGather pg,
-                                                  unsigned long long *wgtrace = nullptr) {
-  if (status != nullptr && *status != ST_RUNNING) return;
-  // MLFF_SYM_TRACE (diagnostic): per workgroup its start, end and units taken
-  if (wgtrace != nullptr && threadIdx.x == 0) wgtrace[3 * blockIdx.x] = wall_clock64();
-  long long units_done = 0;
-  __shared__ double sh[6 * B + 4 * kRB * 64];
-  __shared__ long long s_next;
+// Work counters of k_symv_dyn (sp.ticket): [0] the streaming role's whole tiles (every unit
+// when nothing is generated), [1] k_sym_reduce_w's arrival counter, [2] the generating role's
+// whole tiles, [3] the quarter units either role takes once its own range is exhausted.
+// Every slot reduction resets the three work counters for the next launch.
+constexpr int kTicketWords = 4;
+__device__ __forceinline__ void reset_work_counters(unsigned long long *ticket) {
+  ticket[0] = 0ull;
+  ticket[2] = 0ull;
+  ticket[3] = 0ull;
+}
+
+// next unit of a role (thread 0): its own range [.., hi) through its counter (base = the
+// range's start + the role's workgroups, which took their first unit without an atomic),
+// then -- where the role may -- the shared quarter units; >= nunits: nothing left.  Nobody
+// waits for anybody: a wrong count gives a wrong sum, never a hang.
+__device__ __forceinline__ long long next_unit(unsigned long long *own, long long base, long long hi,
+                                               bool pool, unsigned long long *shared, int nwhole,
+                                               long long nunits, bool &own_done) {
+  if (!own_done) {
+    const long long u = base + (long long)atomicAdd(own, 1ull);
+    if (u < hi) return u;
+    own_done = true;
+  }
+  return pool ? nwhole + (long long)atomicAdd(shared, 1ull) : nunits;
+}
+
+// global index of padded position pos (k_sym_gen_rbf's mapping); false: padding (K is zero)
+__device__ __forceinline__ bool gen_index(const SymGen &gs, int64_t pos, int64_t &g) {
+  const int64_t off = pos % gs.blk;
+  g = (pos / gs.blk) * gs.rows_per + off;
+  return off < gs.rows_per && g < gs.N;
+}
+
+// The lane's 8 columns (2 (lane + 64 q) + e) of a generated tile: their points, zero past d
+// and in the padding (a zero difference adds nothing to the squared distance: fma(0, 0, s)
+// == s), and which of them are inside [0, N)
+struct GenCols {
+  double x[8][kSymGenMaxD];
+  unsigned valid;
+};
+__device__ __forceinline__ void gen_load_cols(const SymGen &gs, int J, int lane, GenCols &gc) {
+  gc.valid = 0u;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    int64_t g;
+    const bool ok = gen_index(gs, (int64_t)J * B + 2 * (lane + 64 * (j >> 1)) + (j & 1), g);
+    if (ok) gc.valid |= 1u << j;
+#pragma unroll
+    for (int t = 0; t < kSymGenMaxD; ++t) gc.x[j][t] = (ok && t < gs.d) ? gs.Xs[g * gs.d + t] : 0.0;
+  }
+}
+// row points of rows [r0, r0 + nr) of tile row block I into LDS: 4 doubles per row, the
+// point (zero past d and in the padding) and 1.0 / 0.0 for inside / padding
+__device__ __forceinline__ void gen_stage_rows(const SymGen &gs, int I, int r0, int nr,
+                                               double *__restrict__ xrow) {
+  for (int i = threadIdx.x; i < nr; i += 256) {
+    int64_t g;
+    const bool ok = gen_index(gs, (int64_t)I * B + r0 + i, g);
+#pragma unroll
+    for (int t = 0; t < kSymGenMaxD; ++t)
+      xrow[4 * (r0 + i) + t] = (ok && t < gs.d) ? gs.Xs[g * gs.d + t] : 0.0;
+    xrow[4 * (r0 + i) + 3] = ok ? 1.0 : 0.0;
+  }
+}
+// every position of block Jb inside [0, N) (positions are valid up to a first padded one)
+__device__ __forceinline__ bool gen_block_full(const SymGen &gs, int Jb) {
+  int64_t g;
+  const int64_t p0 = (int64_t)Jb * B, p1 = p0 + B - 1;
+  return p0 / gs.blk == p1 / gs.blk && gen_index(gs, p0, g) && gen_index(gs, p1, g);
+}
+// row r (tile-local) of a generated tile: the 8 entries of the lane's columns, the bits
+// k_sym_gen_rbf stores.  plain: an off-diagonal tile without padding (no selects)
+__device__ __forceinline__ void gen_row(const SymGen &gs, const GenCols &gc,
+                                        const double *__restrict__ xrow, int r, int lane, bool plain,
+                                        bool diag, d2 (&ar)[4]) {
+  const double *xr = xrow + 4 * r;
+  double x[kSymGenMaxD];
+#pragma unroll
+  for (int t = 0; t < kSymGenMaxD; ++t) x[t] = xr[t];
+  double v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    double s = 0.0;
+#pragma unroll
+    for (int t = 0; t < kSymGenMaxD; ++t) s = rbf_sqdist_step(s, __dsub_rn(gc.x[j][t], x[t]), t == 0);
+    v[j] = rbf_of_sqdist(s);
+  }
+  if (!plain) {
+    const bool rv = xr[3] != 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int c = 2 * (lane + 64 * (j >> 1)) + (j & 1);
+      if (diag && c == r) v[j] = 1.0 + gs.jitter;
+      if (!(rv && ((gc.valid >> j) & 1u))) v[j] = 0.0;
+    }
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q) ar[q] = d2{v[2 * q], v[2 * q + 1]};
+}
+
+// what a k_symv_dyn workgroup needs besides its role
+struct SymvArgs {
+  const double *tiles;
+  const int2 *list;
+  const double *v;
+  double *P, *Pq;
+  int64_t Np;
+  int nwhole;
+  long long nunits;
+  int nb, lsub;
+  PGather pg;
+  double beta;
+};
+
+// The units of one workgroup, first unit u.  GEN: the entries a[rr][q] are evaluated from the
+// points row by row instead of loaded 8 rows ahead; everything that is done with them -- the
+// s0 / s1 chains, the LDS transpose and xor tree, acc over the wave's rows, the 4-wave
+// combine, the slot stores -- is this one body, so both roles write the same bits.
+template <bool GEN>
+__device__ __forceinline__ long long symv_units(const SymvArgs &k, const SymGen &gs, long long u,
+                                                unsigned long long *own, long long base,
+                                                long long hi, bool pool,
+                                                unsigned long long *shared, bool own_done,
+                                                double *__restrict__ sh, long long *s_next) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   double *vrow = sh, *rows = sh + B, *cs = sh + 2 * B;
   double *red = sh + 6 * B + w * kRB * 64;
-  // first unit = blockIdx.x (no atomic burst at launch: one counter word serves ~90
-  // grabs per us); later grabs come from the counter, offset by the grid
-  const long long G = gridDim.x;
-  long long u = blockIdx.x;
-  if (u >= nunits) return;
-  // fused p update: beta from the gathered rho partials (block 0 publishes rho for the slot
-  // reduction, which writes p after every tile has read p_old)
-  double beta = 0.0;
-  if (pg.gb != nullptr) {
-    const double rho = gathered_rho(pg, sh);
-    if (pg.it > 1) beta = rho / pg.st->rho1;
-    if (blockIdx.x == 0 && threadIdx.x == 0) pg.st->rho_new = rho;
-  }
+  double *xrow = sh + 6 * B + 4 * kRB * 64;  // GEN: the unit's row points
+  const PGather &pg = k.pg;
+  const double *v = k.v;
+  const double beta = k.beta;
+  long long units_done = 0;
   int tile, h, gb0, gb1;
-  decode_unit(u, nwhole, lsub, tile, h, gb0, gb1);
-  int2 t = list[tile];
-  const double *A = tiles + (int64_t)tile * B * B;
-  d2 pc[4], a[kRB][4];
+  decode_unit(u, k.nwhole, k.lsub, tile, h, gb0, gb1);
+  int2 t = k.list[tile];
+  const double *A = k.tiles + (int64_t)tile * B * B;
+  d2 pc[4], a[GEN ? 1 : kRB][4];
+  GenCols gc;
   {
 #pragma unroll
     for (int q = 0; q < 4; ++q) pc[q] = pg_val2(pg, v, (int64_t)t.y * B + 2 * (lane + 64 * q), beta);
-    const d2 *rowp = reinterpret_cast<const d2 *>(A + (int64_t)(gb0 + w) * kRB * B) + lane;
+    if (!GEN) {
+      const d2 *rowp = reinterpret_cast<const d2 *>(A + (int64_t)(gb0 + w) * kRB * B) + lane;
 #pragma unroll
-    for (int rr = 0; rr < kRB; ++rr)
+      for (int rr = 0; rr < kRB; ++rr)
 #pragma unroll
-      for (int q = 0; q < 4; ++q) a[rr][q] = __builtin_nontemporal_load(rowp + rr * (B / 2) + 64 * q);
+        for (int q = 0; q < 4; ++q) a[GEN ? 0 : rr][q] = __builtin_nontemporal_load(rowp + rr * (B / 2) + 64 * q);
+    }
   }
-  if (threadIdx.x == 0) s_next = G + (long long)atomicAdd(ticket, 1ull);
+  if (threadIdx.x == 0) *s_next = next_unit(own, base, hi, pool, shared, k.nwhole, k.nunits, own_done);
   for (int i = threadIdx.x; i < (gb1 - gb0) * kRB; i += 256) {
     const int64_t gi = (int64_t)t.x * B + gb0 * kRB + i;
     vrow[gb0 * kRB + i] = pg.gb != nullptr ? pg_val(pg, v, gi, beta) : v[gi];
   }
+  if (GEN) {
+    gen_stage_rows(gs, t.x, gb0 * kRB, (gb1 - gb0) * kRB, xrow);
+    gen_load_cols(gs, t.y, lane, gc);
+  }
   __syncthreads();
   while (true) {
     const bool diag = t.x == t.y;
+    const bool plain = GEN && !diag && gen_block_full(gs, t.x) && gen_block_full(gs, t.y);
     d2 acc[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) acc[q] = d2{0.0, 0.0};
 #pragma unroll 1
     for (int g = gb0 + w; g < gb1; g += 4) {
       const int rbase = g * kRB;
-      if (g != gb0 + w) {
+      if (!GEN && g != gb0 + w) {
         const d2 *rowp = reinterpret_cast<const d2 *>(A + (int64_t)rbase * B) + lane;
 #pragma unroll
         for (int rr = 0; rr < kRB; ++rr)
 #pragma unroll
           for (int q = 0; q < 4; ++q)
-            a[rr][q] = __builtin_nontemporal_load(rowp + rr * (B / 2) + 64 * q);
+            a[GEN ? 0 : rr][q] = __builtin_nontemporal_load(rowp + rr * (B / 2) + 64 * q);
       }
-#pragma unroll
+#pragma unroll(GEN ? 2 : kRB)
       for (int rr = 0; rr < kRB; ++rr) {
-        double s0 = a[rr][0].x * pc[0].x;
-        double s1 = a[rr][0].y * pc[0].y;
+        d2 ar[4];
+        if (GEN) {
+          gen_row(gs, gc, xrow, rbase + rr, lane, plain, diag, ar);
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) ar[q] = a[GEN ? 0 : rr][q];
+        }
+        double s0 = ar[0].x * pc[0].x;
+        double s1 = ar[0].y * pc[0].y;
 #pragma unroll
         for (int q = 1; q < 4; ++q) {
-          s0 = fma(a[rr][q].x, pc[q].x, s0);
-          s1 = fma(a[rr][q].y, pc[q].y, s1);
+          s0 = fma(ar[q].x, pc[q].x, s0);
+          s1 = fma(ar[q].y, pc[q].y, s1);
         }
         red[rr * 64 + lane] = s0 + s1;
         if (!diag) {
           const double pr = vrow[rbase + rr];
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
-            acc[q].x = fma(a[rr][q].x, pr, acc[q].x);
-            acc[q].y = fma(a[rr][q].y, pr, acc[q].y);
+            acc[q].x = fma(ar[q].x, pr, acc[q].x);
+            acc[q].y = fma(ar[q].y, pr, acc[q].y);
           }
         }
       }
@@ -333,39 +454,43 @@ __global__ __launch_bounds__(256) void k_symv_dyn(const double *__restrict__ til
       for (int q = 0; q < 4; ++q) cs2[w * (B / 2) + lane + 64 * q] = acc[q];
     }
     __syncthreads();  // rows / cs complete; s_next visible
-    const long long un = s_next;
+    const long long un = *s_next;
     int tile2 = 0, h2 = 0, gb02 = 0, gb12 = 0;
     int2 t2 = t;
     const double *A2 = A;
-    if (un < nunits) {  // next unit: p segment and first batch in flight during the stores
-      decode_unit(un, nwhole, lsub, tile2, h2, gb02, gb12);
-      t2 = list[tile2];
-      A2 = tiles + (int64_t)tile2 * B * B;
+    if (un < k.nunits) {  // next unit: p segment and first batch in flight during the stores
+      decode_unit(un, k.nwhole, k.lsub, tile2, h2, gb02, gb12);
+      t2 = k.list[tile2];
+      A2 = k.tiles + (int64_t)tile2 * B * B;
 #pragma unroll
       for (int q = 0; q < 4; ++q)
         pc[q] = pg_val2(pg, v, (int64_t)t2.y * B + 2 * (lane + 64 * q), beta);
-      const d2 *rowp = reinterpret_cast<const d2 *>(A2 + (int64_t)(gb02 + w) * kRB * B) + lane;
+      if (GEN) {
+        gen_load_cols(gs, t2.y, lane, gc);
+      } else {
+        const d2 *rowp = reinterpret_cast<const d2 *>(A2 + (int64_t)(gb02 + w) * kRB * B) + lane;
 #pragma unroll
-      for (int rr = 0; rr < kRB; ++rr)
+        for (int rr = 0; rr < kRB; ++rr)
 #pragma unroll
-        for (int q = 0; q < 4; ++q)
-          a[rr][q] = __builtin_nontemporal_load(rowp + rr * (B / 2) + 64 * q);
+          for (int q = 0; q < 4; ++q)
+            a[GEN ? 0 : rr][q] = __builtin_nontemporal_load(rowp + rr * (B / 2) + 64 * q);
+      }
     }
     {
       const int row0 = gb0 * kRB, nr = (gb1 - gb0) * kRB;
-      double *Prow = P + (int64_t)t.y * Np + (int64_t)t.x * B + row0;
+      double *Prow = k.P + (int64_t)t.y * k.Np + (int64_t)t.x * B + row0;
       for (int c = threadIdx.x; c < nr; c += 256) __builtin_nontemporal_store(rows[row0 + c], Prow + c);
       if (!diag) {
-        double *Pc = h == 0 ? P : Pq + (int64_t)(h - 1) * nb * Np;
-        double *Pcol = Pc + (int64_t)t.x * Np + (int64_t)t.y * B;
+        double *Pc = h == 0 ? k.P : k.Pq + (int64_t)(h - 1) * k.nb * k.Np;
+        double *Pcol = Pc + (int64_t)t.x * k.Np + (int64_t)t.y * B;
         for (int c = threadIdx.x; c < B; c += 256)
           __builtin_nontemporal_store((cs[c] + cs[B + c]) + (cs[2 * B + c] + cs[3 * B + c]), Pcol + c);
       }
     }
     __syncthreads();  // LDS consumed, s_next read by everyone
     ++units_done;
-    if (un >= nunits) break;
-    if (threadIdx.x == 0) s_next = G + (long long)atomicAdd(ticket, 1ull);
+    if (un >= k.nunits) break;
+    if (threadIdx.x == 0) *s_next = next_unit(own, base, hi, pool, shared, k.nwhole, k.nunits, own_done);
     tile = tile2;
     h = h2;
     gb0 = gb02;
@@ -376,7 +501,76 @@ __global__ __launch_bounds__(256) void k_symv_dyn(const double *__restrict__ til
       const int64_t gi = (int64_t)t.x * B + gb0 * kRB + i;
       vrow[gb0 * kRB + i] = pg.gb != nullptr ? pg_val(pg, v, gi, beta) : v[gi];
     }
+    if (GEN) gen_stage_rows(gs, t.x, gb0 * kRB, (gb1 - gb0) * kRB, xrow);
     __syncthreads();
+  }
+  return units_done;
+}
+
+// ROLES false: every workgroup streams, one counter over all units (sp.gen off: matrices set
+// by the host, MLFF_SYM_GEN=0, d above kSymGenMaxD).  ROLES true (tiles generated from the
+// RBF points): even workgroups stream the stored whole tiles [0, gs.n_s), odd ones evaluate
+// the whole tiles [gs.n_s, nwhole) from the points instead of reading them; the quarter units
+// go to whoever is done first (gs.qmode 0), to the streaming (1) or the generating role (2).
+template <bool ROLES>
+__global__ __launch_bounds__(256) void k_symv_dyn(const double *__restrict__ tiles,
+                                                  const int2 *__restrict__ list,
+                                                  const double *__restrict__ v,
+                                                  double *__restrict__ P,
+                                                  double *__restrict__ Pq, int64_t Np,
+                                                  int nwhole, long long nunits, int nb,
+                                                  int lsub,
+                                                  unsigned long long *__restrict__ ticket,
+                                                  const int *__restrict__ status, PGather pg,
+                                                  SymGen gs,
+                                                  unsigned long long *wgtrace = nullptr) {
+  if (status != nullptr && *status != ST_RUNNING) return;
+  // MLFF_SYM_TRACE (diagnostic): per workgroup its start, end and units taken
+  if (wgtrace != nullptr && threadIdx.x == 0) wgtrace[3 * blockIdx.x] = wall_clock64();
+  __shared__ double sh[6 * B + 4 * kRB * 64 + (ROLES ? 4 * B : 0)];
+  __shared__ long long s_next;
+  // first unit = the workgroup's index in its role (no atomic burst at launch: one counter
+  // word serves ~90 grabs per us); later grabs come from the counter, offset by the role's
+  // workgroups
+  const bool gen = ROLES && (blockIdx.x & 1u);
+  const long long G = !ROLES ? (long long)gridDim.x : gen ? gridDim.x / 2 : (gridDim.x + 1) / 2;
+  const long long idx = ROLES ? blockIdx.x >> 1 : blockIdx.x;
+  const long long lo = gen ? gs.n_s : 0;
+  const long long hi = !ROLES ? nunits : gen ? nwhole : gs.n_s;
+  const bool pool = ROLES && gs.qmode != (gen ? 1 : 2);
+  if (!ROLES && idx >= nunits) return;
+  // fused p update: beta from the gathered rho partials (block 0 publishes rho for the slot
+  // reduction, which writes p after every tile has read p_old)
+  double beta = 0.0;
+  if (pg.gb != nullptr) {
+    const double rho = gathered_rho(pg, sh);
+    if (pg.it > 1) beta = rho / pg.st->rho1;
+    if (blockIdx.x == 0 && threadIdx.x == 0) pg.st->rho_new = rho;
+  }
+  long long u = lo + idx;
+  bool own_done = false;
+  if (ROLES) {  // a role with fewer whole tiles than workgroups starts in the shared units
+    if (threadIdx.x == 0) {
+      if (u >= hi) {
+        own_done = true;
+        u = pool ? nwhole + (long long)atomicAdd(ticket + 3, 1ull) : nunits;
+      }
+      s_next = u;
+    }
+    __syncthreads();
+    u = s_next;
+    __syncthreads();
+    if (u >= nunits) return;
+  }
+  const SymvArgs k{tiles, list, v, P, Pq, Np, nwhole, nunits, nb, lsub, pg, beta};
+  long long units_done;
+  if constexpr (ROLES) {
+    if (gen)
+      units_done = symv_units<true>(k, gs, u, ticket + 2, lo + G, hi, pool, ticket + 3, own_done, sh, &s_next);
+    else
+      units_done = symv_units<false>(k, gs, u, ticket, lo + G, hi, pool, ticket + 3, own_done, sh, &s_next);
+  } else {
+    units_done = symv_units<false>(k, gs, u, ticket, lo + G, hi, pool, ticket + 3, own_done, sh, &s_next);
   }
   if (wgtrace != nullptr && threadIdx.x == 0) {
     wgtrace[3 * blockIdx.x + 1] = wall_clock64();
@@ -407,7 +601,7 @@ __global__ __launch_bounds__(256) void k_sym_reduce(const double *__restrict__ P
                                                     PGather pg = PGather{},
                                                     double *pw = nullptr) {
   if (status != nullptr && *status != ST_RUNNING) return;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *ticket = 0ull;  // k_symv_dyn's counter
+  if (blockIdx.x == 0 && threadIdx.x == 0) reset_work_counters(ticket);
   double apq = 0.0;
   // one rank, fused p update (PGather): rho as k_symv_dyn summed it, p = fma(beta, p_old, z)
   // written here (every tile has read p_old) and used as the epilogue's v -- k_update_p's bits
@@ -516,7 +710,7 @@ __global__ __launch_bounds__(256) void k_sym_reduce_w(const double *__restrict__
                                                       const int *__restrict__ status,
                                                       PGather pg, PqPublish pub) {
   if (status != nullptr && *status != ST_RUNNING) return;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *ticket = 0ull;  // k_symv_dyn's counter
+  if (blockIdx.x == 0 && threadIdx.x == 0) reset_work_counters(ticket);
   __shared__ double sh[8];
   __shared__ int s_last;
   double apq = 0.0, app = 0.0;
@@ -646,7 +840,7 @@ __global__ __launch_bounds__(256) void k_sym_reduce_wl(const double *__restrict_
                                                        const int *__restrict__ status,
                                                        PGather pg, PqPublish pub) {
   if (status != nullptr && *status != ST_RUNNING) return;
-  if (blockIdx.x == 0 && threadIdx.x == 0) *ticket = 0ull;  // k_symv_dyn's counter
+  if (blockIdx.x == 0 && threadIdx.x == 0) reset_work_counters(ticket);
   __shared__ double sh[8];
   __shared__ int s_last;
   __shared__ int sl[kRwMaxList];
@@ -955,9 +1149,14 @@ void launch_symv(const SymPack &sp, const double *v_full, double *P, const int *
     if (trace_at > 0 && ++launches == trace_at &&
         hipMalloc(&tr, sizeof(unsigned long long) * 3 * G) == hipSuccess)
       (void)hipMemsetAsync(tr, 0, sizeof(unsigned long long) * 3 * G, s);
-    hipLaunchKernelGGL(k_symv_dyn, dim3(G), dim3(256), 0, s,
-                       sp.tiles, sp.list, v_full, P, sp.Pq, sp.Np, (int)sp.nwhole, (long long)grid,
-                       (int)sp.nb, sp.lsub, sp.ticket, status, pg, tr);
+    if (sp.gen)
+      hipLaunchKernelGGL(k_symv_dyn<true>, dim3(G), dim3(256), 0, s,
+                         sp.tiles, sp.list, v_full, P, sp.Pq, sp.Np, (int)sp.nwhole, (long long)grid,
+                         (int)sp.nb, sp.lsub, sp.ticket, status, pg, sp.gsrc, tr);
+    else
+      hipLaunchKernelGGL(k_symv_dyn<false>, dim3(G), dim3(256), 0, s,
+                         sp.tiles, sp.list, v_full, P, sp.Pq, sp.Np, (int)sp.nwhole, (long long)grid,
+                         (int)sp.nb, sp.lsub, sp.ticket, status, pg, SymGen{}, tr);
     if (tr != nullptr) {
       std::vector<unsigned long long> h((size_t)3 * G);
       if (hipStreamSynchronize(s) == hipSuccess &&
@@ -1148,9 +1347,9 @@ int sym_build(mlff_ctx *ctx, bool check_symmetry, bool *symmetric_out) {
     sp.pq_planes = nq;
     MLFF_HIP(ctx, hipMalloc(&sp.split, (size_t)nb * nb));
     MLFF_HIP(ctx, hipMalloc(&sp.own, sizeof(int) * (size_t)nb * (nb + 1)));
-    // [k_symv_dyn's work counter, k_sym_reduce_w's arrival counter]
-    MLFF_HIP(ctx, hipMalloc(&sp.ticket, 2 * sizeof(unsigned long long)));
-    MLFF_HIP(ctx, hipMemsetAsync(sp.ticket, 0, 2 * sizeof(unsigned long long), s));
+    // k_symv_dyn's work counters and k_sym_reduce_w's arrival counter (kTicketWords)
+    MLFF_HIP(ctx, hipMalloc(&sp.ticket, kTicketWords * sizeof(unsigned long long)));
+    MLFF_HIP(ctx, hipMemsetAsync(sp.ticket, 0, kTicketWords * sizeof(unsigned long long), s));
     if (ctx->world > 1) {
       // reduce-scatter operand: rank blocks of blk rows + a tail of p.q shares
       sp.ystride = ctx->blk + round_up(ctx->world, kPad);
@@ -1168,6 +1367,34 @@ int sym_build(mlff_ctx *ctx, bool check_symmetry, bool *symmetric_out) {
   sp.nwhole = nwhole;
   sp.lsub = lsub;
   sp.dyn = dyn;
+  // Generating role (k_symv_dyn<true>): only where the tiles come from the RBF points, which
+  // stay resident, and their dimension fits the role's registers.  The last n_gen whole tiles
+  // are evaluated instead of read; the share follows the two roles' measured rates
+  // (kSymStreamRate / kSymGenRate, common.h).  MLFF_SYM_GEN=0: off (every unit
+  // streamed on the old grid); MLFF_SYM_GEN_TILES=<n>: n generated whole tiles (clamped);
+  // MLFF_SYM_GEN_QUARTERS=0|1|2: the quarter units to either role / streamed / generated.
+  sp.gen = false;
+  sp.gsrc = SymGen{};
+  if (dyn > 0 && nt > 0 && !ctx->has_matrix && ctx->rbf.ready && ctx->rbf.d >= 1 &&
+      ctx->rbf.d <= kSymGenMaxD) {
+    bool on = true;
+    if (const char *e = std::getenv("MLFF_SYM_GEN")) on = std::atoi(e) != 0;
+    int64_t n_s = (int64_t)((double)nwhole * kSymStreamRate / (kSymStreamRate + kSymGenRate) + 0.5);
+    if (const char *e = std::getenv("MLFF_SYM_GEN_TILES"))
+      n_s = nwhole - std::min<int64_t>(nwhole, std::max<int64_t>(0, std::atoll(e)));
+    int qmode = 0;
+    if (const char *e = std::getenv("MLFF_SYM_GEN_QUARTERS")) {
+      const int v = std::atoi(e);
+      if (v >= 0 && v <= 2) qmode = v;
+    }
+    if (nwhole == nt && n_s == nwhole) on = false;                // nothing to generate
+    if (n_s == nwhole && qmode == 1) on = false;                  // every unit streamed
+    if (on) {
+      sp.gen = true;
+      sp.gsrc = SymGen{ctx->rbf.Xs, ctx->rbf.d, ctx->rbf.jitter, ctx->N, ctx->rows_per, ctx->blk,
+                       (int)n_s, qmode};
+    }
+  }
   {
     std::vector<unsigned char> split((size_t)nb * nb, 0);
     sp.t_split = nb;
@@ -1274,6 +1501,8 @@ void sym_free(SymPack &sp) {
   sp.yr = nullptr;
   sp.ntiles = 0;
   sp.pq_planes = 0;
+  sp.gen = false;
+  sp.gsrc = SymGen{};
   sp.ready = false;
 }
 
