@@ -82,13 +82,15 @@ struct SymPack {
   int64_t pq_planes = 0;     // planes allocated in Pq (2^lsub - 1 needed)
   double *Pq = nullptr;
   unsigned char *split = nullptr;  // nb x nb: tile (I, J) is split
-  int *own = nullptr;              // nb x nb owned slots per row block + nb counts (W > 1)
-  // the same slots as a flat load list per row block (W > 1, k_sym_reduce_wl): entry
-  // t | plane << 16 (plane 0 = P, h >= 1 = Pq plane h - 1; a split slot's planes follow it),
-  // pstride entries per row block, then nb counts; pmax = the largest count
+  // nb x nb owned slots per row block (sym_own_entry) + nb counts (W > 1)
+  int *own = nullptr;
+  // the same slots as a flat load list per row block (W > 1, k_sym_reduce_wl): entries
+  // sym_plist_entry(slot, plane) (plane 0 = P, h >= 1 = Pq plane h - 1; a split slot's planes
+  // follow it), pstride entries per row block, then nb counts; pmax = the largest count
   int *plist = nullptr;
   int64_t pstride = 0;
   int pmax = 0;
+  bool pq_ordered = false;         // k_sym_reduce_wl's arrival ordered (MLFF_SYM_PQ_ORDERED=1)
   int64_t t_split = 0;             // smallest I of a split tile (nb if none)
   int64_t dyn = 0;                 // > 0: k_symv_dyn with this many workgroups
   unsigned long long *ticket = nullptr;  // its work counters (reset by the slot reduction)
@@ -98,6 +100,23 @@ struct SymPack {
   double *yr = nullptr;      // world > 1: reduce-scatter result (ystride)
   int64_t ystride = 0;       // blk + tail (p.q shares of every rank)
 };
+
+// Entry formats of SymPack::own and SymPack::plist: the only place their bits are written.
+// own: the slot, kSymOwnSplit set where the slot's tile is split (its planes in Pq);
+// plist: the slot in the low 16 bits, the plane above them.
+constexpr int kSymOwnSplit = 1 << 24;
+constexpr int kSymPlistSlotBits = 16;
+constexpr int kSymPlistMaxSlots = (1 << kSymPlistSlotBits) - 1;  // nb a plist entry can hold
+__host__ __device__ inline int sym_own_entry(int slot, bool split) {
+  return slot | (split ? kSymOwnSplit : 0);
+}
+__host__ __device__ inline int sym_own_slot(int e) { return e & (kSymOwnSplit - 1); }
+__host__ __device__ inline bool sym_own_split(int e) { return (e & kSymOwnSplit) != 0; }
+__host__ __device__ inline int sym_plist_entry(int slot, int plane) {
+  return slot | (plane << kSymPlistSlotBits);
+}
+__host__ __device__ inline int sym_plist_slot(int e) { return e & kSymPlistMaxSlots; }
+__host__ __device__ inline int sym_plist_plane(int e) { return e >> kSymPlistSlotBits; }
 
 // Matrix-free sGDML operator data (kernels_mf.hip).
 struct MfData {
@@ -253,6 +272,21 @@ __device__ __forceinline__ double block_sum256(double v, double *sh) {
   return t;
 }
 
+// block_sum256 of two values at once (sh: 8 doubles), both sums valid in every thread
+__device__ __forceinline__ void block_sum256_pair(double &a, double &b, double *sh) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) {
+    sh[w] = a;
+    sh[4 + w] = b;
+  }
+  __syncthreads();
+  a = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  b = (sh[4] + sh[5]) + (sh[6] + sh[7]);
+}
+
 // Deterministic sum of np partials, broadcast to every thread of the block.
 __device__ __forceinline__ double reduce_parts_bcast(const double *__restrict__ part, int np,
                                                      double *sh) {
@@ -383,8 +417,8 @@ struct mlff_ctx {
   // sharded tiled iteration: k_update_xr_shares folded into the next T r pass (MLFF_FUSE_XR_RANKS=1;
   // off by default: SOLO floors 4.5 us slower at W = 4, equal at W = 8)
   bool fuse_xr_ranks = false;
-  bool pq_publish = false;
-  bool piv_persist_off = false;  // the persistent pivoted Cholesky timed out once (kernels_pivchol.hip)  // MLFF_PQ_PUBLISH=1: the separate k_pq_publish launch (A/B)
+  bool pq_publish = false;       // MLFF_PQ_PUBLISH=1: the separate k_pq_publish launch (A/B)
+  bool piv_persist_off = false;  // the persistent pivoted Cholesky timed out once (kernels_pivchol.hip)
   // Woodbury panel re-orthogonalised by a second CholeskyQR step (MLFF_WB_REFINE, woodbury_inplace;
   // configs[1] at full size: 571 -> 366 iterations, the oracle's 367) and the same for the
   // Nystrom panel (MLFF_NYS_REFINE)

@@ -41,132 +41,17 @@ typedef double d2 __attribute__((ext_vector_type(2)));
 namespace {
 
 constexpr int B = kSymTile;  // 512
-constexpr int kRowsPerWave = B / 4;
 constexpr int kRB = 8;  // rows per batch (loads in flight per wave: kRB x 4 KB)
-
-// 8-row batches [gb0, gb1) of tile (I, J) (64 batches = the whole tile), the batches
-// interleaved over the 4 waves; row partials of those rows to slot J, the segment's
-// column partials to plane Pc (P, or a second plane for a segment that does not start
-// the tile, see sym_build)
-template <bool DIAG>
-__device__ __forceinline__ void tile_body(const double *__restrict__ A, int I, int J,
-                                          const double *__restrict__ v,
-                                          double *__restrict__ P, double *__restrict__ Pc,
-                                          int64_t Np, int gb0, int gb1,
-                                          double *__restrict__ sh) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const d2 *v2 = reinterpret_cast<const d2 *>(v + (int64_t)J * B);
-  d2 pc[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) pc[q] = v2[lane + 64 * q];
-  double *vrow = sh;                       // v[I B .. I B + B)
-  double *rows = sh + B;                   // row partials of the tile
-  double *cs = sh + 2 * B;                 // 4 x B column partials
-  double *red = sh + 6 * B + w * kRB * 64; // wave-private kRB x 64 transpose buffer
-  const int row0 = gb0 * kRB, nrows = (gb1 - gb0) * kRB;
-  if (!DIAG)
-    for (int i = threadIdx.x; i < nrows; i += 256) vrow[row0 + i] = v[(int64_t)I * B + row0 + i];
-  __syncthreads();
-  d2 acc[4];
-#pragma unroll
-  for (int q = 0; q < 4; ++q) acc[q] = d2{0.0, 0.0};
-#pragma unroll 1
-  for (int g = gb0 + w; g < gb1; g += 4) {
-    const int rbase = g * kRB;  // batches interleaved across the 4 waves
-    const d2 *rowp = reinterpret_cast<const d2 *>(A + (int64_t)rbase * B) + lane;
-    d2 a[kRB][4];
-#pragma unroll
-    for (int rr = 0; rr < kRB; ++rr)
-#pragma unroll
-      for (int q = 0; q < 4; ++q) a[rr][q] = __builtin_nontemporal_load(rowp + rr * (B / 2) + 64 * q);
-#pragma unroll
-    for (int rr = 0; rr < kRB; ++rr) {
-      double s0 = a[rr][0].x * pc[0].x;
-      double s1 = a[rr][0].y * pc[0].y;
-#pragma unroll
-      for (int q = 1; q < 4; ++q) {
-        s0 = fma(a[rr][q].x, pc[q].x, s0);
-        s1 = fma(a[rr][q].y, pc[q].y, s1);
-      }
-      red[rr * 64 + lane] = s0 + s1;
-      if (!DIAG) {
-        const double pr = vrow[rbase + rr];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          acc[q].x = fma(a[rr][q].x, pr, acc[q].x);
-          acc[q].y = fma(a[rr][q].y, pr, acc[q].y);
-        }
-      }
-    }
-    // row sums: lane 8 r + c adds lanes 8c .. 8c + 7 of row r, then xor over c
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    const d2 *rp = reinterpret_cast<const d2 *>(red + (lane >> 3) * 64 + (lane & 7) * 8);
-    const d2 t0 = rp[0], t1 = rp[1], t2 = rp[2], t3 = rp[3];
-    double t = ((t0.x + t0.y) + (t1.x + t1.y)) + ((t2.x + t2.y) + (t3.x + t3.y));
-    t += __shfl_xor(t, 1, 64);
-    t += __shfl_xor(t, 2, 64);
-    t += __shfl_xor(t, 4, 64);
-    if ((lane & 7) == 0) rows[rbase + (lane >> 3)] = t;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-  }
-  if (!DIAG) {
-    d2 *cs2 = reinterpret_cast<d2 *>(cs);
-#pragma unroll
-    for (int q = 0; q < 4; ++q) cs2[w * (B / 2) + lane + 64 * q] = acc[q];
-  }
-  __syncthreads();
-  // slot stores are non-temporal: interleaved with the tile stream they cost ~4 %
-  // of the kernel as ordinary stores (scripts/probe_symv.hip)
-  double *Prow = P + (int64_t)J * Np + (int64_t)I * B + row0;
-  for (int c = threadIdx.x; c < nrows; c += 256) __builtin_nontemporal_store(rows[row0 + c], Prow + c);
-  if (!DIAG) {
-    double *Pcol = Pc + (int64_t)I * Np + (int64_t)J * B;
-    for (int c = threadIdx.x; c < B; c += 256)
-      __builtin_nontemporal_store((cs[c] + cs[B + c]) + (cs[2 * B + c] + cs[3 * B + c]), Pcol + c);
-  }
-}
-
-
 constexpr int kBatches = B / kRB;  // 8-row batches per tile
+// LDS doubles of a tile workgroup: v[I B .. I B + B) | the tile's row partials | 4 x B column
+// partials | the 4 waves' private kRB x 64 transpose buffers (| the generating role's row points)
+constexpr int kTileRed = 6 * B;  // the transpose buffers' offset
+constexpr int kTileLds = kTileRed + 4 * kRB * 64;
 
-// workgroups [0, nwhole): one whole tile each; then 2^lsub workgroups per remaining tile,
-// one row slice (512 >> lsub rows) each, so the launch ends on sub-tile units instead of a
-// partial round of whole tiles (a lone 2-MB tile streams at one CU's rate)
-__global__ __launch_bounds__(256) void k_symv_tiles(const double *__restrict__ tiles,
-                                                    const int2 *__restrict__ list,
-                                                    const double *__restrict__ v,
-                                                    double *__restrict__ P,
-                                                    double *__restrict__ Pq, int64_t Np,
-                                                    int nwhole, int nb, int lsub,
-                                                    const int *__restrict__ status) {
-  if (status != nullptr && *status != ST_RUNNING) return;
-  __shared__ double sh[6 * B + 4 * kRB * 64];
-  int tile = blockIdx.x, h = 0, gb0 = 0, gb1 = kBatches;
-  if (tile >= nwhole) {
-    const int u = tile - nwhole;
-    tile = nwhole + (u >> lsub);
-    h = u & ((1 << lsub) - 1);
-    gb0 = h * (kBatches >> lsub);
-    gb1 = gb0 + (kBatches >> lsub);
-  }
-  const int2 t = list[tile];
-  const double *A = tiles + (int64_t)tile * B * B;
-  double *Pc = h == 0 ? P : Pq + (int64_t)(h - 1) * nb * Np;
-  if (t.x == t.y)
-    tile_body<true>(A, t.x, t.y, v, P, Pc, Np, gb0, gb1, sh);
-  else
-    tile_body<false>(A, t.x, t.y, v, P, Pc, Np, gb0, gb1, sh);
-}
-
-// Dynamic persistent schedule with cross-tile prefetch: C resident workgroups take work
-// units (whole tiles, then the quarter units of the tail) from a ticket counter; before
-// finishing a tile (LDS combine + slot stores) a workgroup already has the first batch
-// of its next unit and the next p segment in flight, so the HBM stream of a workgroup
-// slot does not stop at tile boundaries.  The counter is reset by the slot reduction.
+// Work units: [0, nwhole) one whole tile each, then 2^lsub units per remaining tile, one row
+// slice (512 >> lsub rows, batches [gb0, gb1)) each, so a launch ends on sub-tile units instead
+// of a partial round of whole tiles (a lone 2-MB tile streams at one CU's rate).  Sub-unit
+// h > 0 writes its column partials to plane h - 1 of Pq (sym_build).
 __device__ __forceinline__ void decode_unit(long long u, int nwhole, int lsub, int &tile, int &h,
                                             int &gb0, int &gb1) {
   if (u < nwhole) {
@@ -230,6 +115,15 @@ __device__ __forceinline__ d2 pg_val2(const PGather &pg, const double *v, int64_
   if (pg.it <= 1) return z;
   const d2 po = *reinterpret_cast<const d2 *>(v + i);
   return d2{fma(beta, po.x, z.x), fma(beta, po.y, z.y)};
+}
+
+// beta of the fused p update from the iteration's rho; block 0 passes rho on (k_symv_dyn, which
+// summed it: to st->rho_new for the slot reduction; the slot reduction, which writes p after
+// every tile has read p_old: to st->rho)
+__device__ __forceinline__ double fused_p_beta(const PGather &pg, double rho, double *publish) {
+  const double beta = pg.it > 1 ? rho / pg.st->rho1 : 0.0;
+  if (blockIdx.x == 0 && threadIdx.x == 0) *publish = rho;
+  return beta;
 }
 
 // Work counters of k_symv_dyn (sp.ticket): [0] the streaming role's whole tiles (every unit
@@ -332,6 +226,135 @@ __device__ __forceinline__ void gen_row(const SymGen &gs, const GenCols &gc,
   for (int q = 0; q < 4; ++q) ar[q] = d2{v[2 * q], v[2 * q + 1]};
 }
 
+// ---- the tile body: what both schedules (k_symv_tiles, k_symv_dyn) and both roles do with a
+// unit, written once so that they all store the same bits ----
+
+// 8 rows [rbase, rbase + kRB) of the stored tile A, the lane's 4 double2 columns of each
+__device__ __forceinline__ void tile_load_batch(const double *A, int64_t rbase, int lane,
+                                                d2 (&a)[kRB][4]) {
+  const d2 *rowp = reinterpret_cast<const d2 *>(A + rbase * B) + lane;
+#pragma unroll
+  for (int rr = 0; rr < kRB; ++rr)
+#pragma unroll
+    for (int q = 0; q < 4; ++q) a[rr][q] = __builtin_nontemporal_load(rowp + rr * (B / 2) + 64 * q);
+}
+
+// One batch of 8 rows against the operand columns pc: the rows' partials summed over the 64
+// lanes into rows[] (wave-private LDS transpose: lane 8 r + c adds lanes 8c .. 8c + 7 of row
+// r, then xor over c), the lane's column partials into acc (off the diagonal).  GEN: the
+// entries are evaluated from the points row by row instead of taken from the loaded batch a.
+template <bool GEN>
+__device__ __forceinline__ void tile_batch(const d2 (&a)[GEN ? 1 : kRB][4], const SymGen &gs,
+                                           const GenCols &gc, const double *xrow,
+                                           bool plain, bool diag, const d2 (&pc)[4],
+                                           const double *vrow, int rbase, int lane,
+                                           double *red, double *rows,
+                                           d2 (&acc)[4]) {
+#pragma unroll(GEN ? 2 : kRB)
+  for (int rr = 0; rr < kRB; ++rr) {
+    d2 ar[4];
+    if constexpr (GEN) {
+      gen_row(gs, gc, xrow, rbase + rr, lane, plain, diag, ar);
+    } else {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) ar[q] = a[rr][q];
+    }
+    double s0 = ar[0].x * pc[0].x;
+    double s1 = ar[0].y * pc[0].y;
+#pragma unroll
+    for (int q = 1; q < 4; ++q) {
+      s0 = fma(ar[q].x, pc[q].x, s0);
+      s1 = fma(ar[q].y, pc[q].y, s1);
+    }
+    red[rr * 64 + lane] = s0 + s1;
+    if (!diag) {
+      const double pr = vrow[rbase + rr];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        acc[q].x = fma(ar[q].x, pr, acc[q].x);
+        acc[q].y = fma(ar[q].y, pr, acc[q].y);
+      }
+    }
+  }
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const d2 *rp = reinterpret_cast<const d2 *>(red + (lane >> 3) * 64 + (lane & 7) * 8);
+  const d2 t0 = rp[0], t1 = rp[1], t2 = rp[2], t3 = rp[3];
+  double tt = ((t0.x + t0.y) + (t1.x + t1.y)) + ((t2.x + t2.y) + (t3.x + t3.y));
+  tt += __shfl_xor(tt, 1, 64);
+  tt += __shfl_xor(tt, 2, 64);
+  tt += __shfl_xor(tt, 4, 64);
+  if ((lane & 7) == 0) rows[rbase + (lane >> 3)] = tt;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The wave's column partials of a unit into LDS for the 4-wave combine of tile_store_slots
+__device__ __forceinline__ void tile_stage_cols(const d2 (&acc)[4], double *cs, int w, int lane) {
+  d2 *cs2 = reinterpret_cast<d2 *>(cs);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) cs2[w * (B / 2) + lane + 64 * q] = acc[q];
+}
+
+// The unit's slot stores: row partials to slot J of rows I B + .., the 4 waves' column partials
+// combined to slot I of rows J B + .. (plane P for sub-unit 0, else Pq plane h - 1).
+// Non-temporal: interleaved with the tile stream they cost ~4 % of the kernel as ordinary
+// stores (scripts/probe_symv.hip)
+__device__ __forceinline__ void tile_store_slots(double *P, double *Pq,
+                                                 int64_t Np, int nb, int2 t, int h, int gb0, int gb1,
+                                                 bool diag, const double *sh) {
+  const double *rows = sh + B, *cs = sh + 2 * B;
+  const int row0 = gb0 * kRB, nr = (gb1 - gb0) * kRB;
+  double *Prow = P + (int64_t)t.y * Np + (int64_t)t.x * B + row0;
+  for (int c = threadIdx.x; c < nr; c += 256) __builtin_nontemporal_store(rows[row0 + c], Prow + c);
+  if (!diag) {
+    double *Pc = h == 0 ? P : Pq + (int64_t)(h - 1) * nb * Np;
+    double *Pcol = Pc + (int64_t)t.x * Np + (int64_t)t.y * B;
+    for (int c = threadIdx.x; c < B; c += 256)
+      __builtin_nontemporal_store((cs[c] + cs[B + c]) + (cs[2 * B + c] + cs[3 * B + c]), Pcol + c);
+  }
+}
+
+// MLFF_SYM_SCHED=static: one workgroup per unit, the tile body once
+__global__ __launch_bounds__(256) void k_symv_tiles(const double *__restrict__ tiles,
+                                                    const int2 *__restrict__ list,
+                                                    const double *__restrict__ v,
+                                                    double *__restrict__ P,
+                                                    double *__restrict__ Pq, int64_t Np,
+                                                    int nwhole, int nb, int lsub,
+                                                    const int *__restrict__ status) {
+  if (status != nullptr && *status != ST_RUNNING) return;
+  __shared__ double sh[kTileLds];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  int tile, h, gb0, gb1;
+  decode_unit(blockIdx.x, nwhole, lsub, tile, h, gb0, gb1);
+  const int2 t = list[tile];
+  const double *A = tiles + (int64_t)tile * B * B;
+  d2 pc[4], a[kRB][4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+    pc[q] = *reinterpret_cast<const d2 *>(v + (int64_t)t.y * B + 2 * (lane + 64 * q));
+  tile_load_batch(A, (int64_t)(gb0 + w) * kRB, lane, a);
+  for (int i = gb0 * kRB + threadIdx.x; i < gb1 * kRB; i += 256) sh[i] = v[(int64_t)t.x * B + i];
+  __syncthreads();
+  const bool diag = t.x == t.y;
+  const GenCols none{};
+  d2 acc[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) acc[q] = d2{0.0, 0.0};
+#pragma unroll 1
+  for (int g = gb0 + w; g < gb1; g += 4) {
+    if (g != gb0 + w) tile_load_batch(A, g * kRB, lane, a);
+    tile_batch<false>(a, SymGen{}, none, nullptr, false, diag, pc, sh, g * kRB, lane,
+                      sh + kTileRed + w * kRB * 64, sh + B, acc);
+  }
+  if (!diag) tile_stage_cols(acc, sh + 2 * B, w, lane);
+  __syncthreads();
+  tile_store_slots(P, Pq, Np, nb, t, h, gb0, gb1, diag, sh);
+}
+
 // what a k_symv_dyn workgroup needs besides its role
 struct SymvArgs {
   const double *tiles;
@@ -346,10 +369,16 @@ struct SymvArgs {
   double beta;
 };
 
-// The units of one workgroup, first unit u.  GEN: the entries a[rr][q] are evaluated from the
-// points row by row instead of loaded 8 rows ahead; everything that is done with them -- the
-// s0 / s1 chains, the LDS transpose and xor tree, acc over the wave's rows, the 4-wave
-// combine, the slot stores -- is this one body, so both roles write the same bits.
+// Dynamic persistent schedule with cross-tile prefetch: C resident workgroups take work
+// units (whole tiles, then the quarter units of the tail) from a ticket counter; before
+// finishing a tile (LDS combine + slot stores) a workgroup already has the first batch
+// of its next unit and the next p segment in flight, so the HBM stream of a workgroup
+// slot does not stop at tile boundaries.  The counter is reset by the slot reduction.
+//
+// The units of one workgroup, first unit u.  Both roles run the tile body above; they differ
+// in where a unit's entries come from (GEN: the points, else the stream 8 rows ahead).
+// (The operand reads -- pc before a unit, vrow after the previous one's stores -- stay spelled
+// out at their two places each: as helpers they are scheduled differently, 2 VGPRs more.)
 template <bool GEN>
 __device__ __forceinline__ long long symv_units(const SymvArgs &k, const SymGen &gs, long long u,
                                                 unsigned long long *own, long long base,
@@ -358,8 +387,8 @@ __device__ __forceinline__ long long symv_units(const SymvArgs &k, const SymGen 
                                                 double *__restrict__ sh, long long *s_next) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   double *vrow = sh, *rows = sh + B, *cs = sh + 2 * B;
-  double *red = sh + 6 * B + w * kRB * 64;
-  double *xrow = sh + 6 * B + 4 * kRB * 64;  // GEN: the unit's row points
+  double *red = sh + kTileRed + w * kRB * 64;
+  double *xrow = sh + kTileLds;  // GEN: the unit's row points
   const PGather &pg = k.pg;
   const double *v = k.v;
   const double beta = k.beta;
@@ -370,17 +399,9 @@ __device__ __forceinline__ long long symv_units(const SymvArgs &k, const SymGen 
   const double *A = k.tiles + (int64_t)tile * B * B;
   d2 pc[4], a[GEN ? 1 : kRB][4];
   GenCols gc;
-  {
 #pragma unroll
-    for (int q = 0; q < 4; ++q) pc[q] = pg_val2(pg, v, (int64_t)t.y * B + 2 * (lane + 64 * q), beta);
-    if (!GEN) {
-      const d2 *rowp = reinterpret_cast<const d2 *>(A + (int64_t)(gb0 + w) * kRB * B) + lane;
-#pragma unroll
-      for (int rr = 0; rr < kRB; ++rr)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) a[GEN ? 0 : rr][q] = __builtin_nontemporal_load(rowp + rr * (B / 2) + 64 * q);
-    }
-  }
+  for (int q = 0; q < 4; ++q) pc[q] = pg_val2(pg, v, (int64_t)t.y * B + 2 * (lane + 64 * q), beta);
+  if constexpr (!GEN) tile_load_batch(A, (int64_t)(gb0 + w) * kRB, lane, a);
   if (threadIdx.x == 0) *s_next = next_unit(own, base, hi, pool, shared, k.nwhole, k.nunits, own_done);
   for (int i = threadIdx.x; i < (gb1 - gb0) * kRB; i += 256) {
     const int64_t gi = (int64_t)t.x * B + gb0 * kRB + i;
@@ -399,60 +420,11 @@ __device__ __forceinline__ long long symv_units(const SymvArgs &k, const SymGen 
     for (int q = 0; q < 4; ++q) acc[q] = d2{0.0, 0.0};
 #pragma unroll 1
     for (int g = gb0 + w; g < gb1; g += 4) {
-      const int rbase = g * kRB;
-      if (!GEN && g != gb0 + w) {
-        const d2 *rowp = reinterpret_cast<const d2 *>(A + (int64_t)rbase * B) + lane;
-#pragma unroll
-        for (int rr = 0; rr < kRB; ++rr)
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            a[GEN ? 0 : rr][q] = __builtin_nontemporal_load(rowp + rr * (B / 2) + 64 * q);
-      }
-#pragma unroll(GEN ? 2 : kRB)
-      for (int rr = 0; rr < kRB; ++rr) {
-        d2 ar[4];
-        if (GEN) {
-          gen_row(gs, gc, xrow, rbase + rr, lane, plain, diag, ar);
-        } else {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) ar[q] = a[GEN ? 0 : rr][q];
-        }
-        double s0 = ar[0].x * pc[0].x;
-        double s1 = ar[0].y * pc[0].y;
-#pragma unroll
-        for (int q = 1; q < 4; ++q) {
-          s0 = fma(ar[q].x, pc[q].x, s0);
-          s1 = fma(ar[q].y, pc[q].y, s1);
-        }
-        red[rr * 64 + lane] = s0 + s1;
-        if (!diag) {
-          const double pr = vrow[rbase + rr];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            acc[q].x = fma(ar[q].x, pr, acc[q].x);
-            acc[q].y = fma(ar[q].y, pr, acc[q].y);
-          }
-        }
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-      const d2 *rp = reinterpret_cast<const d2 *>(red + (lane >> 3) * 64 + (lane & 7) * 8);
-      const d2 t0 = rp[0], t1 = rp[1], t2 = rp[2], t3 = rp[3];
-      double tt = ((t0.x + t0.y) + (t1.x + t1.y)) + ((t2.x + t2.y) + (t3.x + t3.y));
-      tt += __shfl_xor(tt, 1, 64);
-      tt += __shfl_xor(tt, 2, 64);
-      tt += __shfl_xor(tt, 4, 64);
-      if ((lane & 7) == 0) rows[rbase + (lane >> 3)] = tt;
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      if constexpr (!GEN)
+        if (g != gb0 + w) tile_load_batch(A, g * kRB, lane, a);
+      tile_batch<GEN>(a, gs, gc, xrow, plain, diag, pc, vrow, g * kRB, lane, red, rows, acc);
     }
-    if (!diag) {
-      d2 *cs2 = reinterpret_cast<d2 *>(cs);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) cs2[w * (B / 2) + lane + 64 * q] = acc[q];
-    }
+    if (!diag) tile_stage_cols(acc, cs, w, lane);
     __syncthreads();  // rows / cs complete; s_next visible
     const long long un = *s_next;
     int tile2 = 0, h2 = 0, gb02 = 0, gb12 = 0;
@@ -465,28 +437,12 @@ __device__ __forceinline__ long long symv_units(const SymvArgs &k, const SymGen 
 #pragma unroll
       for (int q = 0; q < 4; ++q)
         pc[q] = pg_val2(pg, v, (int64_t)t2.y * B + 2 * (lane + 64 * q), beta);
-      if (GEN) {
+      if constexpr (GEN)
         gen_load_cols(gs, t2.y, lane, gc);
-      } else {
-        const d2 *rowp = reinterpret_cast<const d2 *>(A2 + (int64_t)(gb02 + w) * kRB * B) + lane;
-#pragma unroll
-        for (int rr = 0; rr < kRB; ++rr)
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            a[GEN ? 0 : rr][q] = __builtin_nontemporal_load(rowp + rr * (B / 2) + 64 * q);
-      }
+      else
+        tile_load_batch(A2, (int64_t)(gb02 + w) * kRB, lane, a);
     }
-    {
-      const int row0 = gb0 * kRB, nr = (gb1 - gb0) * kRB;
-      double *Prow = k.P + (int64_t)t.y * k.Np + (int64_t)t.x * B + row0;
-      for (int c = threadIdx.x; c < nr; c += 256) __builtin_nontemporal_store(rows[row0 + c], Prow + c);
-      if (!diag) {
-        double *Pc = h == 0 ? k.P : k.Pq + (int64_t)(h - 1) * k.nb * k.Np;
-        double *Pcol = Pc + (int64_t)t.x * k.Np + (int64_t)t.y * B;
-        for (int c = threadIdx.x; c < B; c += 256)
-          __builtin_nontemporal_store((cs[c] + cs[B + c]) + (cs[2 * B + c] + cs[3 * B + c]), Pcol + c);
-      }
-    }
+    tile_store_slots(k.P, k.Pq, k.Np, k.nb, t, h, gb0, gb1, diag, sh);
     __syncthreads();  // LDS consumed, s_next read by everyone
     ++units_done;
     if (un >= k.nunits) break;
@@ -527,7 +483,7 @@ __global__ __launch_bounds__(256) void k_symv_dyn(const double *__restrict__ til
   if (status != nullptr && *status != ST_RUNNING) return;
   // MLFF_SYM_TRACE (diagnostic): per workgroup its start, end and units taken
   if (wgtrace != nullptr && threadIdx.x == 0) wgtrace[3 * blockIdx.x] = wall_clock64();
-  __shared__ double sh[6 * B + 4 * kRB * 64 + (ROLES ? 4 * B : 0)];
+  __shared__ double sh[kTileLds + (ROLES ? 4 * B : 0)];
   __shared__ long long s_next;
   // first unit = the workgroup's index in its role (no atomic burst at launch: one counter
   // word serves ~90 grabs per us); later grabs come from the counter, offset by the role's
@@ -539,14 +495,7 @@ __global__ __launch_bounds__(256) void k_symv_dyn(const double *__restrict__ til
   const long long hi = !ROLES ? nunits : gen ? nwhole : gs.n_s;
   const bool pool = ROLES && gs.qmode != (gen ? 1 : 2);
   if (!ROLES && idx >= nunits) return;
-  // fused p update: beta from the gathered rho partials (block 0 publishes rho for the slot
-  // reduction, which writes p after every tile has read p_old)
-  double beta = 0.0;
-  if (pg.gb != nullptr) {
-    const double rho = gathered_rho(pg, sh);
-    if (pg.it > 1) beta = rho / pg.st->rho1;
-    if (blockIdx.x == 0 && threadIdx.x == 0) pg.st->rho_new = rho;
-  }
+  const double beta = pg.gb != nullptr ? fused_p_beta(pg, gathered_rho(pg, sh), &pg.st->rho_new) : 0.0;
   long long u = lo + idx;
   bool own_done = false;
   if (ROLES) {  // a role with fewer whole tiles than workgroups starts in the shared units
@@ -578,15 +527,10 @@ __global__ __launch_bounds__(256) void k_symv_dyn(const double *__restrict__ til
   }
 }
 
-// column partials of slot t for rows of block bi: tile (t, bi), t > bi; a split tile
-// adds its sub-units 1..nq (planes Pq) to sub-unit 0 (P) in sub-unit order
-constexpr int kOwnSplit = 1 << 24;  // flag bit of an owned-slot entry: the tile is split
-
-// y[i] = sum_{t=0}^{nb-1} P[t, i] over the slots whose tile this rank owns
-// (all slots on one rank); EPI: y = sigma * y + lam * vloc for rows < n_out
-// y[i] = sum_{t=0}^{nb-1} of the slots of row i (one rank); EPI: y = sigma y + lam vloc;
-// PQ (with EPI): also the p.q partial sums (vloc = p) of each workgroup -> pq_part
-// (grid = kVecGrid workgroups, grid-stride over the rows)
+// one rank: y[i] = the sum of the nb slots of row i in slot order, a split slot as
+// ((P + Pq0) + Pq1) + ...; EPI: y = sigma y + lam vloc for rows < n_out; PQ (with EPI): also the
+// p.q partial sum (vloc = p) of each workgroup -> pq_part (grid = kVecGrid workgroups,
+// grid-stride over the rows)
 template <bool EPI, bool PQ>
 __global__ __launch_bounds__(256) void k_sym_reduce(const double *__restrict__ P,
                                                     const double *__restrict__ Pq,
@@ -603,14 +547,9 @@ __global__ __launch_bounds__(256) void k_sym_reduce(const double *__restrict__ P
   if (status != nullptr && *status != ST_RUNNING) return;
   if (blockIdx.x == 0 && threadIdx.x == 0) reset_work_counters(ticket);
   double apq = 0.0;
-  // one rank, fused p update (PGather): rho as k_symv_dyn summed it, p = fma(beta, p_old, z)
-  // written here (every tile has read p_old) and used as the epilogue's v -- k_update_p's bits
-  double beta = 0.0;
-  if (PQ && pg.gb != nullptr) {
-    const double rho = pg.st->rho_new;
-    if (pg.it > 1) beta = rho / pg.st->rho1;
-    if (blockIdx.x == 0 && threadIdx.x == 0) pg.st->rho = rho;
-  }
+  // fused p update (PGather): p = fma(beta, p_old, z) written here and used as the epilogue's v
+  // -- k_update_p's bits
+  const double beta = PQ && pg.gb != nullptr ? fused_p_beta(pg, pg.st->rho_new, &pg.st->rho) : 0.0;
   const int64_t pl = (int64_t)nb * Np;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n_out;
        i += (int64_t)gridDim.x * 256) {
@@ -674,26 +613,126 @@ __global__ __launch_bounds__(256) void k_sym_reduce(const double *__restrict__ P
   }
   if (PQ) {
     __shared__ double sh[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) apq += __shfl_down(apq, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = apq;
-    __syncthreads();
-    if (threadIdx.x == 0) pq_part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    apq = block_sum256(apq, sh);
+    if (threadIdx.x == 0) pq_part[blockIdx.x] = apq;
   }
+}
+
+// ---- p.q of the sharded iteration: every rank publishes its share, sigma p.y_g + lam
+// ||p_loc||^2, from the (apq, app) partial pairs of its reduction's workgroups ----
+struct PqPublish {
+  double sigma = 0.0, lam = 0.0;
+  int world = 0;  // 0: the separate k_pq_publish launch follows (MLFF_PQ_PUBLISH=1)
+  bool ordered = true;  // the arrival's form (pq_put), k_sym_reduce_wl only
+};
+
+// How a workgroup's pair travels to the workgroup that arrives last (pq_arrive):
+//  ORDERED   plain stores, an agent-scope release before the ticket add, an agent-scope acquire
+//            in the last workgroup, plain loads: the pairs' stores happen before their loads
+//            under the HIP memory model (the adds on the one word form a release sequence).
+//  !ORDERED  relaxed agent-scope atomic stores (write-through, sc1) drained with s_waitcnt
+//            vmcnt(0) before a relaxed add, relaxed agent-scope atomic loads (sc1, past the L1)
+//            in the last workgroup.  Nothing synchronises in the language's model; on gfx950 it
+//            is the counter form of cdna_hip_programming.md Guideline 16 (R1: every payload
+//            store sc1 and drained by the storing wave before the add; every load of it sc1)
+//            and the first row of the sc1 hand-off table in MI355X_MICROARCH.md, "inter-
+//            workgroup visibility" (one lane of each workgroup signals for its own stores by
+//            an agent-scope add on one counter, the last adder's workgroup loads behind a
+//            barrier; measured there at one workgroup per CU, this grid puts two on a CU).
+//            Observed behaviour of gfx950, not an architectural guarantee.  It spares
+//            every workgroup the release's L2 write-back: one rank of 8 at N = 65536, rank 0 /
+//            rank 3, 0.3528 / 0.3490 ms per iteration against 0.3583 / 0.3621 ms ORDERED
+//            (medians of three interleaved pairs, profiles/symrefactor/ab/summary.txt).
+//            k_sym_reduce_wl's default; MLFF_SYM_PQ_ORDERED=1 at the operator's build selects
+//            ORDERED there.  k_sym_reduce_w is always ORDERED.
+template <bool ORDERED>
+__device__ __forceinline__ void pq_put(double *p, double v) {
+  if (ORDERED)
+    *p = v;
+  else
+    __hip_atomic_store(reinterpret_cast<unsigned long long *>(p), __builtin_bit_cast(unsigned long long, v),
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <bool ORDERED>
+__device__ __forceinline__ double pq_get(const double *p) {
+  if (ORDERED) return *p;
+  return __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<const unsigned long long *>(p),
+                                                      __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+
+// s_rank = sigma * sum(pq_part) + lam * sum(pp_part) (one workgroup; fixed order: thread f adds
+// partials f, f + 256, ..., then block_sum256_pair), put into tail slot `rank` of every rank
+// block of the reduce-scatter operand; the other tail slots stay zero, so the reduce-scatter
+// hands every rank the exact vector of shares (x + 0 is exact in any order) and each rank sums
+// it in rank order: p.q is bitwise identical on all ranks without a separate allreduce.
+template <bool ORDERED = true>
+__device__ __forceinline__ void pq_publish_share(const double *pq_part, const double *pp_part, int np,
+                                                 double sigma, double lam, int rank, int world,
+                                                 int64_t blk, int64_t bstride, double *yg, double *sh) {
+  double a = 0.0, b = 0.0;
+  for (int i = threadIdx.x; i < np; i += 256) {
+    a += pq_get<ORDERED>(pq_part + i);
+    b += pq_get<ORDERED>(pp_part + i);
+  }
+  block_sum256_pair(a, b, sh);
+  const double share = sigma * a + lam * b;
+  for (int g = threadIdx.x; g < world; g += 256) yg[(int64_t)g * bstride + blk + rank] = share;
+}
+
+// Arrival of a workgroup whose pair (a, b) thread 0 holds: the pair is stored, then the
+// workgroup takes a ticket (ticket[1]).  True in every thread of the workgroup that arrived
+// last, which resets the ticket for the next launch and may read every pair (pq_get).
+template <bool ORDERED>
+__device__ __forceinline__ bool pq_arrive(double a, double b, double *pq_part, double *pp_part,
+                                          unsigned long long *ticket, int *s_last) {
+  if (threadIdx.x == 0) {
+    pq_put<ORDERED>(pq_part + blockIdx.x, a);
+    pq_put<ORDERED>(pp_part + blockIdx.x, b);
+    if (ORDERED)
+      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    else
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    const bool last = __hip_atomic_fetch_add(ticket + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
+                      (unsigned long long)(gridDim.x - 1);
+    if (last) __hip_atomic_store(ticket + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    *s_last = last;
+  }
+  __syncthreads();
+  if (!*s_last) return false;
+  // !ORDERED: no instruction, it only keeps the compiler from moving the loads above the ticket
+  if (ORDERED)
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+  else
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  return true;
+}
+
+// The end of a rank reduction's workgroup: its pair summed over the workgroup and stored; with
+// the folded publish the last workgroup to arrive also does k_pq_publish's work -- the same
+// sums in the same order, so the same share bits -- one launch less per sharded iteration (the
+// publish was a 4.9 us single-workgroup launch at W = 8).  sh: 8 doubles.
+template <bool ORDERED>
+__device__ __forceinline__ void pq_tail(double apq, double app, double *pq_part, double *pp_part,
+                                        unsigned long long *ticket, const PqPublish &pub, int rank,
+                                        int64_t blk, int64_t bstride, double *yg, double *sh,
+                                        int *s_last) {
+  block_sum256_pair(apq, app, sh);
+  if (pub.world == 0) {
+    if (threadIdx.x == 0) {
+      pq_part[blockIdx.x] = apq;
+      pp_part[blockIdx.x] = app;
+    }
+    return;
+  }
+  if (!pq_arrive<ORDERED>(apq, app, pq_part, pp_part, ticket, s_last)) return;
+  pq_publish_share<ORDERED>(pq_part, pp_part, (int)gridDim.x, pub.sigma, pub.lam, rank, pub.world, blk,
+                            bstride, yg, sh);
 }
 
 // several ranks: y_g = sum over this rank's slots for every row of [0, ld), written
 // into rank blocks of stride `bstride` (= blk + tail: the reduce-scatter operand).
 // PQ: also the partial p.y_g (all rows) + (lam/sigma-free) ||p_loc||^2 partials, one
-// pair per workgroup (fixed order), for k_pq_publish.
-// PQ: the last workgroup to finish (arrival counter ticket[1], reset by it) also does
-// k_pq_publish's work -- the same sums in the same order, so the same share bits -- one launch
-// less per sharded iteration (the publish was a 4.9 us single-workgroup launch at W = 8)
-struct PqPublish {
-  double sigma = 0.0, lam = 0.0;
-  int world = 0;
-};
-
+// pair per workgroup (pq_tail).
 template <bool PQ>
 __global__ __launch_bounds__(256) void k_sym_reduce_w(const double *__restrict__ P,
                                                       const double *__restrict__ Pq,
@@ -714,13 +753,8 @@ __global__ __launch_bounds__(256) void k_sym_reduce_w(const double *__restrict__
   __shared__ double sh[8];
   __shared__ int s_last;
   double apq = 0.0, app = 0.0;
-  // fused p update: rho as k_symv_dyn summed it, p written here (every tile has read p_old)
-  double beta = 0.0;
-  if (PQ && pg.gb != nullptr) {
-    const double rho = pg.st->rho_new;
-    if (pg.it > 1) beta = rho / pg.st->rho1;
-    if (blockIdx.x == 0 && threadIdx.x == 0) pg.st->rho = rho;
-  }
+  // fused p update: p written here (every tile has read p_old)
+  const double beta = PQ && pg.gb != nullptr ? fused_p_beta(pg, pg.st->rho_new, &pg.st->rho) : 0.0;
   const int64_t lo = (int64_t)rank * blk, hi = lo + blk;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < ld;
        i += (int64_t)gridDim.x * 256) {
@@ -728,8 +762,8 @@ __global__ __launch_bounds__(256) void k_sym_reduce_w(const double *__restrict__
     // wave-uniform (scalar loads), so no slot load waits on a flag or index load
     const int bi = __builtin_amdgcn_readfirstlane((int)(i / B));
     double s = 0.0;
-    // this rank's slots of row block bi (own: ascending slots, kOwnSplit marks a split
-    // tile; built at setup) in batches of 16 whose loads are all in flight before the
+    // this rank's slots of row block bi (own: ascending sym_own_entry slots, the flag marks a
+    // split tile; built at setup) in batches of 16 whose loads are all in flight before the
     // first addition; every slot value is ((P + Pq0) + Pq1) + ... (nq planes), added in
     // slot order
     const int *ol = own + (int64_t)bi * nb;
@@ -742,9 +776,9 @@ __global__ __launch_bounds__(256) void k_sym_reduce_w(const double *__restrict__
         v[u] = 0.0;
         if (c + u < cnt) {
           const int e = ol[c + u];
-          const int64_t at = (int64_t)(e & (kOwnSplit - 1)) * Np + i;
+          const int64_t at = (int64_t)sym_own_slot(e) * Np + i;
           v[u] = P[at];
-          if (e & kOwnSplit)
+          if (sym_own_split(e))
             for (int hq = 0; hq < nq; ++hq) v[u] += Pq[hq * pl + at];
         }
       }
@@ -765,52 +799,7 @@ __global__ __launch_bounds__(256) void k_sym_reduce_w(const double *__restrict__
       if (i >= lo && i < hi) app = fma(pv, pv, app);
     }
   }
-  if (PQ) {
-    double t = apq;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
-    double u = app;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) u += __shfl_down(u, o, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-      sh[w] = t;
-      sh[4 + w] = u;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      pq_part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-      pp_part[blockIdx.x] = (sh[4] + sh[5]) + (sh[6] + sh[7]);
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-      s_last = atomicAdd(ticket + 1, 1ull) == (unsigned long long)(gridDim.x - 1);
-    }
-    __syncthreads();
-    if (!s_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    // k_pq_publish: s_rank = sigma sum(pq_part) + lam sum(pp_part), into tail slot `rank` of
-    // every rank block of the reduce-scatter operand
-    const int np = (int)gridDim.x;
-    double a = 0.0, b = 0.0;
-    for (int i = threadIdx.x; i < np; i += 256) {
-      a += pq_part[i];
-      b += pp_part[i];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      a += __shfl_down(a, o, 64);
-      b += __shfl_down(b, o, 64);
-    }
-    __syncthreads();
-    if (lane == 0) {
-      sh[w] = a;
-      sh[4 + w] = b;
-    }
-    __syncthreads();
-    const double share = pub.sigma * ((sh[0] + sh[1]) + (sh[2] + sh[3])) +
-                         pub.lam * ((sh[4] + sh[5]) + (sh[6] + sh[7]));
-    for (int g = threadIdx.x; g < pub.world; g += 256) yg[(int64_t)g * bstride + blk + rank] = share;
-    if (threadIdx.x == 0) ticket[1] = 0ull;
-  }
+  if (PQ) pq_tail<true>(apq, app, pq_part, pp_part, ticket, pub, rank, blk, bstride, yg, sh, &s_last);
 }
 
 // k_sym_reduce_w with the slot loads of a row all in flight (round 6): at
@@ -824,7 +813,7 @@ __global__ __launch_bounds__(256) void k_sym_reduce_w(const double *__restrict__
 // order -- each slot ((P + Pq0) + Pq1) + ..., the slots in ascending order: k_sym_reduce_w's
 // sums, the same bits (MLFF_SYM_REDUCE_LIST=0 restores it; test_sym_reduce_list_bitwise)
 constexpr int kRwBatch = 32;
-constexpr int kRwMaxList = 2048;
+constexpr int kRwMaxList = 2048;  // list entries per row block staged in LDS
 
 template <bool PQ>
 __global__ __launch_bounds__(256) void k_sym_reduce_wl(const double *__restrict__ P,
@@ -845,12 +834,8 @@ __global__ __launch_bounds__(256) void k_sym_reduce_wl(const double *__restrict_
   __shared__ int s_last;
   __shared__ int sl[kRwMaxList];
   double apq = 0.0, app = 0.0;
-  double beta = 0.0;
-  if (PQ && pg.gb != nullptr) {
-    const double rho = pg.st->rho_new;
-    if (pg.it > 1) beta = rho / pg.st->rho1;
-    if (blockIdx.x == 0 && threadIdx.x == 0) pg.st->rho = rho;
-  }
+  // fused p update: p written here (every tile has read p_old)
+  const double beta = PQ && pg.gb != nullptr ? fused_p_beta(pg, pg.st->rho_new, &pg.st->rho) : 0.0;
   const int64_t lo = (int64_t)rank * blk, hi = lo + blk;
   const int64_t plane = (int64_t)nb * Np;
   for (int64_t c0 = (int64_t)blockIdx.x * 256; c0 < ld; c0 += (int64_t)gridDim.x * 256) {
@@ -885,9 +870,9 @@ __global__ __launch_bounds__(256) void k_sym_reduce_wl(const double *__restrict_
     auto entries = [&](int e0) { return sl[e0 + lane32 < cnt ? e0 + lane32 : cnt - 1]; };
     auto load = [&](int ent, int u) {
       const int x = __builtin_amdgcn_readlane(ent, u);
-      const int h = x >> 16;
+      const int h = sym_plist_plane(x);
       const double *base = h == 0 ? P : Pq + (int64_t)(h - 1) * plane;
-      return base[(int64_t)(x & 0xffff) * Np + i];
+      return base[(int64_t)sym_plist_slot(x) * Np + i];
     };
     double s = 0.0, cur = 0.0;
     if (cnt > 0 && i < ld) {
@@ -908,7 +893,7 @@ __global__ __launch_bounds__(256) void k_sym_reduce_wl(const double *__restrict_
 #pragma unroll
         for (int u = 0; u < kRwBatch; ++u) {
           if (e0 + u < cnt) {
-            if (__builtin_amdgcn_readlane(ev, u) >> 16) {
+            if (sym_plist_plane(__builtin_amdgcn_readlane(ev, u))) {
               cur += v[u];  // a split slot's next plane
             } else {
               s += cur;  // the previous slot is complete
@@ -937,76 +922,14 @@ __global__ __launch_bounds__(256) void k_sym_reduce_wl(const double *__restrict_
     }
   }
   if (PQ) {
-    double t = apq;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) t += __shfl_down(t, o, 64);
-    double u = app;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) u += __shfl_down(u, o, 64);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-      sh[w] = t;
-      sh[4 + w] = u;
-    }
-    __syncthreads();
-    // the last-arriving workgroup publishes this rank's share.  Each workgroup's two partials are
-    // stored write-through (sc1: agent-scope relaxed atomic stores) and drained before its ticket
-    // add, and the last arriver reads them with sc1 loads only, so no agent-scope release fence
-    // (an L2 write-back per workgroup: k_sym_reduce_w's form) and no acquire are needed
-    // (cdna_hip_programming.md Guideline 16, R1 / the counter form)
-    if (threadIdx.x == 0) {
-      const double a0 = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-      const double b0 = (sh[4] + sh[5]) + (sh[6] + sh[7]);
-      if (pub.world > 0) {
-        __hip_atomic_store(reinterpret_cast<unsigned long long *>(pq_part) + blockIdx.x,
-                           __builtin_bit_cast(unsigned long long, a0), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(reinterpret_cast<unsigned long long *>(pp_part) + blockIdx.x,
-                           __builtin_bit_cast(unsigned long long, b0), __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_last = __hip_atomic_fetch_add(ticket + 1, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) ==
-                 (unsigned long long)(gridDim.x - 1);
-      } else {
-        pq_part[blockIdx.x] = a0;
-        pp_part[blockIdx.x] = b0;
-      }
-    }
-    if (pub.world == 0) return;  // the separate k_pq_publish launch follows
-    __syncthreads();
-    if (!s_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");  // no loads above the ticket
-    const int np = (int)gridDim.x;
-    double a = 0.0, b = 0.0;
-    for (int q = threadIdx.x; q < np; q += 256) {
-      a += __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<unsigned long long *>(pq_part) + q,
-                                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      b += __builtin_bit_cast(double, __hip_atomic_load(reinterpret_cast<unsigned long long *>(pp_part) + q,
-                                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      a += __shfl_down(a, o, 64);
-      b += __shfl_down(b, o, 64);
-    }
-    __syncthreads();
-    if (lane == 0) {
-      sh[w] = a;
-      sh[4 + w] = b;
-    }
-    __syncthreads();
-    const double share = pub.sigma * ((sh[0] + sh[1]) + (sh[2] + sh[3])) +
-                         pub.lam * ((sh[4] + sh[5]) + (sh[6] + sh[7]));
-    for (int g = threadIdx.x; g < pub.world; g += 256) yg[(int64_t)g * bstride + blk + rank] = share;
-    if (threadIdx.x == 0) __hip_atomic_store(ticket + 1, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (pub.ordered)
+      pq_tail<true>(apq, app, pq_part, pp_part, ticket, pub, rank, blk, bstride, yg, sh, &s_last);
+    else
+      pq_tail<false>(apq, app, pq_part, pp_part, ticket, pub, rank, blk, bstride, yg, sh, &s_last);
   }
 }
 
-// s_rank = sigma * sum(pq_part) + lam * sum(pp_part) (this rank's share of p.q), put
-// into tail slot `rank` of every rank block of the reduce-scatter operand; the other
-// tail slots stay zero, so the reduce-scatter hands every rank the exact vector of
-// shares (x + 0 is exact in any order) and each rank sums it in rank order: p.q is
-// bitwise identical on all ranks without a separate allreduce.
+// MLFF_PQ_PUBLISH=1 (A/B): pq_publish_share as a launch of its own, one workgroup
 __global__ __launch_bounds__(256) void k_pq_publish(const double *__restrict__ pq_part,
                                                     const double *__restrict__ pp_part, int np,
                                                     double sigma, double lam, int rank, int world,
@@ -1015,25 +938,7 @@ __global__ __launch_bounds__(256) void k_pq_publish(const double *__restrict__ p
                                                     const int *__restrict__ status) {
   if (status != nullptr && *status != ST_RUNNING) return;
   __shared__ double sh[8];
-  double a = 0.0, b = 0.0;
-  for (int i = threadIdx.x; i < np; i += 256) {
-    a += pq_part[i];
-    b += pp_part[i];
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a += __shfl_down(a, o, 64);
-    b += __shfl_down(b, o, 64);
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) {
-    sh[w] = a;
-    sh[4 + w] = b;
-  }
-  __syncthreads();
-  const double share = sigma * ((sh[0] + sh[1]) + (sh[2] + sh[3])) +
-                       lam * ((sh[4] + sh[5]) + (sh[6] + sh[7]));
-  for (int g = threadIdx.x; g < world; g += 256) yg[(int64_t)g * bstride + blk + rank] = share;
+  pq_publish_share(pq_part, pp_part, np, sigma, lam, rank, world, blk, bstride, yg, sh);
 }
 
 // y[i] = sigma * src[i] + lam * vloc[i]  (src may alias y)
@@ -1131,72 +1036,131 @@ __global__ __launch_bounds__(256) void k_sym_gen_rbf(const int2 *__restrict__ li
 
 }  // namespace
 
+// The MLFF_SYM_* environment knobs (all A/B or diagnostic; the defaults are the measured
+// choices).  Read at every operator build, so a process may change them between contexts.
+struct SymKnobs {
+  // MLFF_SYM_WHOLE_ROUNDS=<r>: at most r rounds of whole tiles, the rest split (finer units for
+  // the dynamic schedule where a rank holds only ~2 tiles per resident workgroup, W = 8)
+  int64_t whole_rounds = -1;
+  // Sub-units per split tile: 4 (quarters).  MLFF_SYM_LSUB=3|4 slices the split tiles
+  // into 8 / 16 row slices instead (the count that would fill the C slots when the nt mod
+  // C tail tiles are few, e.g. 8 of a rank's 1032 at 8 ranks).  Measured on one MI355X
+  // (scripts/gpu_sym_lsub_ab.sh, profiles/r02/final3e): no gain -- the dynamic schedule
+  // already overlaps the tail (k_symv_dyn 323.9 vs 323.6 us at W = 8) while the reduce
+  // reads 15 instead of 3 planes of the split slots (12.7 -> 17.9 us): the step got 1 %
+  // slower at W = 8 / 4, 0.2 % at W = 1.  Kept selectable, not default.
+  int lsub = 2;
+  // launch schedule: k_symv_dyn (C resident workgroups taking units from a counter, next
+  // unit prefetched across tile boundaries) -- measured on one MI355X: 2.51 ms at 8256
+  // tiles where one-workgroup-per-unit launches took 2.51-2.61 ms (bimodal across runs),
+  // equal at 528 / 1035 tiles.  MLFF_SYM_SCHED=static selects the one-workgroup-per-unit
+  // launch (k_symv_tiles).
+  // (A persistent schedule -- exactly C workgroups streaming equal batch ranges, tiles
+  // cut at range boundaries -- measured slower at every size on one MI355X: 2.67 vs
+  // 2.61 ms at 8256 tiles, 0.366 vs 0.338 ms at 1035: the hardware dispatcher's dynamic
+  // whole-tile balance beats a static equal-byte split.)
+  bool dynamic = true;
+  // Generating role (k_symv_dyn<true>).  MLFF_SYM_GEN=0: off (every unit streamed on the old
+  // grid); MLFF_SYM_GEN_TILES=<n>: n generated whole tiles (clamped) instead of the modelled
+  // share; MLFF_SYM_GEN_QUARTERS=0|1|2: the quarter units to either role / streamed / generated.
+  bool gen = true;
+  int64_t gen_tiles = -1;
+  int gen_quarters = 0;
+  // MLFF_SYM_REDUCE_LIST=0: k_sym_reduce_w instead of k_sym_reduce_wl (W > 1)
+  bool reduce_list = true;
+  // MLFF_SYM_PQ_ORDERED=1: k_sym_reduce_wl's arrival in the formally ordered form (pq_put)
+  bool pq_ordered = false;
+  // MLFF_SYM_TRACE=<n> (diagnostic): the n-th k_symv_dyn launch of the
+  // process records each workgroup's start / end / units and prints where the tile stream's
+  // time goes (print_symv_trace); launch_symv keeps the value of its first call
+  long long trace_at = 0;
+};
+
+static SymKnobs sym_knobs() {
+  SymKnobs k;
+  if (const char *e = std::getenv("MLFF_SYM_WHOLE_ROUNDS")) k.whole_rounds = std::max<int64_t>(0, std::atoll(e));
+  if (const char *e = std::getenv("MLFF_SYM_LSUB")) {
+    const int v = std::atoi(e);
+    if (v >= 1 && v <= 4) k.lsub = v;
+  }
+  if (const char *e = std::getenv("MLFF_SYM_SCHED")) k.dynamic = std::strcmp(e, "static") != 0;
+  if (const char *e = std::getenv("MLFF_SYM_GEN")) k.gen = std::atoi(e) != 0;
+  if (const char *e = std::getenv("MLFF_SYM_GEN_TILES")) k.gen_tiles = std::max<int64_t>(0, std::atoll(e));
+  if (const char *e = std::getenv("MLFF_SYM_GEN_QUARTERS")) {
+    const int v = std::atoi(e);
+    if (v >= 0 && v <= 2) k.gen_quarters = v;
+  }
+  if (const char *e = std::getenv("MLFF_SYM_REDUCE_LIST")) k.reduce_list = std::atoi(e) != 0;
+  if (const char *e = std::getenv("MLFF_SYM_PQ_ORDERED")) k.pq_ordered = std::atoi(e) != 0;
+  if (const char *e = std::getenv("MLFF_SYM_TRACE")) k.trace_at = std::atoll(e);
+  return k;
+}
+
+// MLFF_SYM_TRACE: the ramp until every workgroup runs, the tail after the median one is done
+// (tr: start, end (10-ns ticks) and units of each of the G workgroups; one sync)
+static void print_symv_trace(const unsigned long long *tr, unsigned G, int64_t units, hipStream_t s) {
+  std::vector<unsigned long long> h((size_t)3 * G);
+  if (hipStreamSynchronize(s) != hipSuccess ||
+      hipMemcpy(h.data(), tr, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost) != hipSuccess)
+    return;
+  unsigned long long t0 = ~0ull, t1 = 0;
+  std::vector<double> st, en, un;
+  for (unsigned g = 0; g < G; ++g) {
+    if (h[3 * g] == 0) continue;
+    t0 = std::min(t0, h[3 * g]);
+    t1 = std::max(t1, h[3 * g + 1]);
+  }
+  double idle = 0.0;
+  for (unsigned g = 0; g < G; ++g) {
+    if (h[3 * g] == 0) continue;
+    st.push_back(10.0 * (double)(h[3 * g] - t0));
+    en.push_back(10.0 * (double)(h[3 * g + 1] - t0));
+    un.push_back((double)h[3 * g + 2]);
+    idle += 10.0 * (double)(t1 - h[3 * g + 1]) + 10.0 * (double)(h[3 * g] - t0);
+  }
+  auto q = [](std::vector<double> v, double f) {
+    std::sort(v.begin(), v.end());
+    return v.empty() ? 0.0 : v[(size_t)(f * (double)(v.size() - 1))];
+  };
+  const double span = 10.0 * (double)(t1 - t0);
+  std::fprintf(stderr,
+               "[sym trace] units %lld on %zu workgroups (units per wg p0/p50/p100 %.0f/%.0f/%.0f); "
+               "span %.1f us; starts p50/p100 %.1f/%.1f us; ends p0/p10/p50/p90/p100 "
+               "%.1f/%.1f/%.1f/%.1f/%.1f us; idle (ramp + tail) %.1f %% of wg-time\n",
+               (long long)units, st.size(), q(un, 0.0), q(un, 0.5), q(un, 1.0), 1e-3 * span,
+               1e-3 * q(st, 0.5), 1e-3 * q(st, 1.0), 1e-3 * q(en, 0.0), 1e-3 * q(en, 0.1),
+               1e-3 * q(en, 0.5), 1e-3 * q(en, 0.9), 1e-3 * q(en, 1.0),
+               100.0 * idle / (span * (double)st.size()));
+}
+
 void launch_symv(const SymPack &sp, const double *v_full, double *P, const int *status,
                  hipStream_t s, PGather pg) {
   if (sp.ntiles == 0) return;
   const int64_t grid = sp.nwhole + ((sp.ntiles - sp.nwhole) << sp.lsub);
-  if (sp.dyn > 0) {
-    const unsigned G = (unsigned)std::min<int64_t>(sp.dyn, grid);
-    // MLFF_SYM_TRACE=<n> (diagnostic): the n-th launch of the process records
-    // each workgroup's start / end / units and prints where the tile stream's time goes (the
-    // ramp until every workgroup runs, the tail after the median one is done); one sync
-    static const long long trace_at = [] {
-      const char *e = std::getenv("MLFF_SYM_TRACE");
-      return e ? std::atoll(e) : 0ll;
-    }();
-    static long long launches = 0;
-    unsigned long long *tr = nullptr;
-    if (trace_at > 0 && ++launches == trace_at &&
-        hipMalloc(&tr, sizeof(unsigned long long) * 3 * G) == hipSuccess)
-      (void)hipMemsetAsync(tr, 0, sizeof(unsigned long long) * 3 * G, s);
-    if (sp.gen)
-      hipLaunchKernelGGL(k_symv_dyn<true>, dim3(G), dim3(256), 0, s,
-                         sp.tiles, sp.list, v_full, P, sp.Pq, sp.Np, (int)sp.nwhole, (long long)grid,
-                         (int)sp.nb, sp.lsub, sp.ticket, status, pg, sp.gsrc, tr);
-    else
-      hipLaunchKernelGGL(k_symv_dyn<false>, dim3(G), dim3(256), 0, s,
-                         sp.tiles, sp.list, v_full, P, sp.Pq, sp.Np, (int)sp.nwhole, (long long)grid,
-                         (int)sp.nb, sp.lsub, sp.ticket, status, pg, SymGen{}, tr);
-    if (tr != nullptr) {
-      std::vector<unsigned long long> h((size_t)3 * G);
-      if (hipStreamSynchronize(s) == hipSuccess &&
-          hipMemcpy(h.data(), tr, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost) ==
-              hipSuccess) {
-        unsigned long long t0 = ~0ull, t1 = 0;
-        std::vector<double> st, en, un;
-        for (unsigned g = 0; g < G; ++g) {
-          if (h[3 * g] == 0) continue;
-          t0 = std::min(t0, h[3 * g]);
-          t1 = std::max(t1, h[3 * g + 1]);
-        }
-        double idle = 0.0;
-        for (unsigned g = 0; g < G; ++g) {
-          if (h[3 * g] == 0) continue;
-          st.push_back(10.0 * (double)(h[3 * g] - t0));
-          en.push_back(10.0 * (double)(h[3 * g + 1] - t0));
-          un.push_back((double)h[3 * g + 2]);
-          idle += 10.0 * (double)(t1 - h[3 * g + 1]) + 10.0 * (double)(h[3 * g] - t0);
-        }
-        auto q = [](std::vector<double> v, double f) {
-          std::sort(v.begin(), v.end());
-          return v.empty() ? 0.0 : v[(size_t)(f * (double)(v.size() - 1))];
-        };
-        const double span = 10.0 * (double)(t1 - t0);
-        std::fprintf(stderr,
-                     "[sym trace] units %lld on %zu workgroups (units per wg p0/p50/p100 %.0f/%.0f/%.0f); "
-                     "span %.1f us; starts p50/p100 %.1f/%.1f us; ends p0/p10/p50/p90/p100 "
-                     "%.1f/%.1f/%.1f/%.1f/%.1f us; idle (ramp + tail) %.1f %% of wg-time\n",
-                     (long long)grid, st.size(), q(un, 0.0), q(un, 0.5), q(un, 1.0), 1e-3 * span,
-                     1e-3 * q(st, 0.5), 1e-3 * q(st, 1.0), 1e-3 * q(en, 0.0), 1e-3 * q(en, 0.1),
-                     1e-3 * q(en, 0.5), 1e-3 * q(en, 0.9), 1e-3 * q(en, 1.0),
-                     100.0 * idle / (span * (double)st.size()));
-      }
-      (void)hipFree(tr);
-    }
+  if (sp.dyn == 0) {
+    hipLaunchKernelGGL(k_symv_tiles, dim3((unsigned)grid), dim3(256), 0, s, sp.tiles, sp.list, v_full,
+                       P, sp.Pq, sp.Np, (int)sp.nwhole, (int)sp.nb, sp.lsub, status);
     return;
   }
-  hipLaunchKernelGGL(k_symv_tiles, dim3((unsigned)grid), dim3(256), 0, s, sp.tiles, sp.list, v_full,
-                     P, sp.Pq, sp.Np, (int)sp.nwhole, (int)sp.nb, sp.lsub, status);
+  const unsigned G = (unsigned)std::min<int64_t>(sp.dyn, grid);
+  static const long long trace_at = sym_knobs().trace_at;
+  static long long launches = 0;
+  unsigned long long *tr = nullptr;
+  if (trace_at > 0 && ++launches == trace_at &&
+      hipMalloc(&tr, sizeof(unsigned long long) * 3 * G) == hipSuccess)
+    (void)hipMemsetAsync(tr, 0, sizeof(unsigned long long) * 3 * G, s);
+  if (sp.gen)
+    hipLaunchKernelGGL(k_symv_dyn<true>, dim3(G), dim3(256), 0, s,
+                       sp.tiles, sp.list, v_full, P, sp.Pq, sp.Np, (int)sp.nwhole, (long long)grid,
+                       (int)sp.nb, sp.lsub, sp.ticket, status, pg, sp.gsrc, tr);
+  else
+    hipLaunchKernelGGL(k_symv_dyn<false>, dim3(G), dim3(256), 0, s,
+                       sp.tiles, sp.list, v_full, P, sp.Pq, sp.Np, (int)sp.nwhole, (long long)grid,
+                       (int)sp.nb, sp.lsub, sp.ticket, status, pg, SymGen{}, tr);
+  if (tr != nullptr) {
+    print_symv_trace(tr, G, grid, s);
+    (void)hipFree(tr);
+  }
 }
 
 void launch_sym_reduce(const SymPack &sp, int64_t n_out, double *y, bool epilogue, double sigma,
@@ -1222,10 +1186,10 @@ void launch_sym_reduce_pq(const SymPack &sp, int64_t n_out, double *y, double si
                      sp.ticket, status, pg, pg.gb != nullptr ? const_cast<double *>(p) : nullptr);
 }
 
-// k_sym_reduce_wl unless MLFF_SYM_REDUCE_LIST=0 at the operator's build (A/B: k_sym_reduce_w);
-// the list form needs the row block's list in LDS (kRwMaxList)
+// k_sym_reduce_wl where the operator's build made its list (not with MLFF_SYM_REDUCE_LIST=0,
+// A/B: k_sym_reduce_w) and the list fits: a row block's entries in LDS, the slot in an entry
 static bool sym_reduce_list(const SymPack &sp) {
-  return sp.plist != nullptr && sp.pstride <= kRwMaxList && sp.nb <= 0xffff;
+  return sp.plist != nullptr && sp.pstride <= kRwMaxList && sp.nb <= kSymPlistMaxSlots;
 }
 
 void launch_sym_reduce_ranks(const SymPack &sp, int rank, int world, int64_t blk,
@@ -1235,8 +1199,9 @@ void launch_sym_reduce_ranks(const SymPack &sp, int rank, int world, int64_t blk
   const int64_t ld = (int64_t)world * blk;
   const dim3 grid(kVecGrid);
   double *pw = const_cast<double *>(p_full);  // written only when the p update is fused
-  const PqPublish pub = p_full == nullptr ? PqPublish{}
-                                          : PqPublish{sigma, lam, separate_publish ? 0 : world};
+  const PqPublish pub = p_full == nullptr
+                            ? PqPublish{}
+                            : PqPublish{sigma, lam, separate_publish ? 0 : world, sp.pq_ordered};
   const PGather pgu = p_full == nullptr ? PGather{} : pg;
   if (sym_reduce_list(sp)) {
     if (p_full == nullptr)
@@ -1251,12 +1216,12 @@ void launch_sym_reduce_ranks(const SymPack &sp, int rank, int world, int64_t blk
     hipLaunchKernelGGL((k_sym_reduce_w<false>), grid, dim3(256), 0, s, sp.P, sp.Pq, sp.split, sp.Np,
                        (1 << sp.lsub) - 1, (int)sp.nb, rank,
                        sp.own, ld, blk, sp.ystride, sp.yg, pw, pq_part, pp_part,
-                       sp.ticket, status, PGather{}, PqPublish{});
+                       sp.ticket, status, pgu, pub);
   } else {
     hipLaunchKernelGGL((k_sym_reduce_w<true>), grid, dim3(256), 0, s, sp.P, sp.Pq, sp.split, sp.Np,
                        (1 << sp.lsub) - 1, (int)sp.nb, rank,
                        sp.own, ld, blk, sp.ystride, sp.yg, pw, pq_part, pp_part,
-                       sp.ticket, status, pg, pub);
+                       sp.ticket, status, pgu, pub);
   }
   if (p_full != nullptr && separate_publish)  // MLFF_PQ_PUBLISH=1 (ctx->pq_publish): A/B
     hipLaunchKernelGGL(k_pq_publish, dim3(1), dim3(256), 0, s, pq_part, pp_part, kVecGrid, sigma, lam,
@@ -1278,22 +1243,35 @@ static int owner_host(int I, int J, int tpr) {
   return ((I + J) & 1) ? a : c;
 }
 
-int sym_build(mlff_ctx *ctx, bool check_symmetry, bool *symmetric_out) {
-  SymPack &sp = ctx->sym;
-  hipStream_t s = ctx->stream;
-  const int64_t Np = round_up(ctx->ld, B);
-  const int nb = (int)(Np / B);
+// ---- sym_build: plan, allocate, slot tables, fill ----
+
+// What this rank stores and how the mat-vec runs over it
+struct SymPlan {
+  int64_t Np = 0;
+  int nb = 0, tpr = 0;              // row blocks; tiles per rank block
+  std::vector<int2> list;           // the rank's tiles
+  std::vector<unsigned char> trans; // packed from the mirror rows (the row block is another rank's)
+  int64_t nt = 0, nwhole = 0;
+  int lsub = 2;
+  int64_t nq = 3;                   // Pq planes: 2^lsub - 1
+  int64_t dyn = 0;                  // resident workgroups of k_symv_dyn, 0: k_symv_tiles
+  bool gen = false;
+  SymGen gsrc;
+};
+
+static SymPlan sym_plan(const mlff_ctx *ctx, const SymKnobs &kn) {
+  SymPlan pl;
+  pl.Np = round_up(ctx->ld, B);
+  pl.nb = (int)(pl.Np / B);
   // tiles per rank block: blk is a multiple of B when world > 1 (mlff_ctx_create)
-  const int tpr = ctx->world > 1 ? (int)(ctx->blk / B) : nb;
-  std::vector<int2> list;
-  std::vector<unsigned char> trans;
-  for (int I = 0; I < nb; ++I)
+  pl.tpr = ctx->world > 1 ? (int)(ctx->blk / B) : pl.nb;
+  for (int I = 0; I < pl.nb; ++I)
     for (int J = 0; J <= I; ++J) {
-      if (owner_host(I, J, tpr) != ctx->rank) continue;
-      list.push_back(make_int2(I, J));
-      trans.push_back(ctx->world > 1 && (I / tpr) != ctx->rank ? 1 : 0);
+      if (owner_host(I, J, pl.tpr) != ctx->rank) continue;
+      pl.list.push_back(make_int2(I, J));
+      pl.trans.push_back(ctx->world > 1 && (I / pl.tpr) != ctx->rank ? 1 : 0);
     }
-  const int64_t nt = (int64_t)list.size();
+  pl.nt = (int64_t)pl.list.size();
   // Tail split: with C workgroups resident at once (2 per CU: 208 VGPRs -> 2 waves per
   // SIMD), whole tiles fill floor(nt / C) full rounds and the nt mod C remaining tiles
   // run as quarters instead of a partial round of lone 2-MB tiles.  Measured (one
@@ -1304,50 +1282,51 @@ int sym_build(mlff_ctx *ctx, bool check_symmetry, bool *symmetric_out) {
       cus < 1)
     cus = 256;
   const int64_t C = 2 * (int64_t)cus;
-  int64_t nwhole = (nt / C) * C;
-  // MLFF_SYM_WHOLE_ROUNDS=<r> (A/B): at most r rounds of whole tiles, the rest split (finer units
-  // for the dynamic schedule where a rank holds only ~2 tiles per resident workgroup, W = 8)
-  if (const char *e = std::getenv("MLFF_SYM_WHOLE_ROUNDS"))
-    nwhole = std::min<int64_t>(nwhole, std::max<int64_t>(0, std::atoll(e)) * C);
-  // launch schedule: k_symv_dyn (C resident workgroups taking units from a counter, next
-  // unit prefetched across tile boundaries) -- measured on one MI355X: 2.51 ms at 8256
-  // tiles where one-workgroup-per-unit launches took 2.51-2.61 ms (bimodal across runs),
-  // equal at 528 / 1035 tiles.  MLFF_SYM_SCHED=static selects the one-workgroup-per-unit
-  // launch (k_symv_tiles).
-  // Sub-units per split tile: 4 (quarters).  MLFF_SYM_LSUB=3|4 slices the split tiles
-  // into 8 / 16 row slices instead (the count that would fill the C slots when the nt mod
-  // C tail tiles are few, e.g. 8 of a rank's 1032 at 8 ranks).  Measured on one MI355X
-  // (scripts/gpu_sym_lsub_ab.sh, profiles/r02/final3e): no gain -- the dynamic schedule
-  // already overlaps the tail (k_symv_dyn 323.9 vs 323.6 us at W = 8) while the reduce
-  // reads 15 instead of 3 planes of the split slots (12.7 -> 17.9 us): the step got 1 %
-  // slower at W = 8 / 4, 0.2 % at W = 1.  Kept selectable, not default.
-  int lsub = 2;
-  if (const char *e = std::getenv("MLFF_SYM_LSUB")) {
-    const int v = std::atoi(e);
-    if (v >= 1 && v <= 4) lsub = v;
+  pl.nwhole = (pl.nt / C) * C;
+  if (kn.whole_rounds >= 0) pl.nwhole = std::min<int64_t>(pl.nwhole, kn.whole_rounds * C);
+  pl.lsub = kn.lsub;
+  pl.nq = ((int64_t)1 << pl.lsub) - 1;
+  pl.dyn = kn.dynamic ? C : 0;
+  // Generating role (k_symv_dyn<true>): only where the tiles come from the RBF points, which
+  // stay resident, and their dimension fits the role's registers.  The last n_gen whole tiles
+  // are evaluated instead of read; the share follows the two roles' measured rates
+  // (kSymStreamRate / kSymGenRate, common.h).
+  if (pl.dyn > 0 && pl.nt > 0 && !ctx->has_matrix && ctx->rbf.ready && ctx->rbf.d >= 1 &&
+      ctx->rbf.d <= kSymGenMaxD) {
+    int64_t n_s = (int64_t)((double)pl.nwhole * kSymStreamRate / (kSymStreamRate + kSymGenRate) + 0.5);
+    if (kn.gen_tiles >= 0) n_s = pl.nwhole - std::min<int64_t>(pl.nwhole, kn.gen_tiles);
+    const int qmode = kn.gen_quarters;
+    bool on = kn.gen;
+    if (pl.nwhole == pl.nt && n_s == pl.nwhole) on = false;  // nothing to generate
+    if (n_s == pl.nwhole && qmode == 1) on = false;          // every unit streamed
+    if (on) {
+      pl.gen = true;
+      pl.gsrc = SymGen{ctx->rbf.Xs, ctx->rbf.d, ctx->rbf.jitter, ctx->N, ctx->rows_per, ctx->blk,
+                       (int)n_s, qmode};
+    }
   }
-  const int64_t nq = ((int64_t)1 << lsub) - 1;
-  int64_t dyn = C;
-  if (const char *e = std::getenv("MLFF_SYM_SCHED"))
-    if (std::strcmp(e, "static") == 0) dyn = 0;
-  // (A persistent schedule -- exactly C workgroups streaming equal batch ranges, tiles
-  // cut at range boundaries -- measured slower at every size on one MI355X: 2.67 vs
-  // 2.61 ms at 8256 tiles, 0.366 vs 0.338 ms at 1035: the hardware dispatcher's dynamic
-  // whole-tile balance beats a static equal-byte split.)
+  return pl;
+}
+
+// device buffers for the plan (kept when the sizes did not change), and the plan into sp
+static int sym_alloc(mlff_ctx *ctx, const SymPlan &pl, const SymKnobs &kn) {
+  SymPack &sp = ctx->sym;
+  hipStream_t s = ctx->stream;
+  const int64_t nt = pl.nt, nb = pl.nb, Np = pl.Np, nq = pl.nq;
   if (sp.tiles == nullptr || sp.ntiles != nt || sp.Np != Np || sp.pq_planes != nq) {
     sym_free(sp);
     if (nt > 0) {
       MLFF_HIP(ctx, hipMalloc(&sp.tiles, sizeof(double) * nt * B * B));
       MLFF_HIP(ctx, hipMalloc(&sp.list, sizeof(int2) * nt));
     }
-    MLFF_HIP(ctx, hipMalloc(&sp.P, sizeof(double) * (int64_t)nb * Np));
-    MLFF_HIP(ctx, hipMemsetAsync(sp.P, 0, sizeof(double) * (int64_t)nb * Np, s));
-    MLFF_HIP(ctx, hipMalloc(&sp.Pq, sizeof(double) * nq * (int64_t)nb * Np));
-    MLFF_HIP(ctx, hipMemsetAsync(sp.Pq, 0, sizeof(double) * nq * (int64_t)nb * Np, s));
+    MLFF_HIP(ctx, hipMalloc(&sp.P, sizeof(double) * nb * Np));
+    MLFF_HIP(ctx, hipMemsetAsync(sp.P, 0, sizeof(double) * nb * Np, s));
+    MLFF_HIP(ctx, hipMalloc(&sp.Pq, sizeof(double) * nq * nb * Np));
+    MLFF_HIP(ctx, hipMemsetAsync(sp.Pq, 0, sizeof(double) * nq * nb * Np, s));
     sp.pq_planes = nq;
     MLFF_HIP(ctx, hipMalloc(&sp.split, (size_t)nb * nb));
     MLFF_HIP(ctx, hipMalloc(&sp.own, sizeof(int) * (size_t)nb * (nb + 1)));
-    // k_symv_dyn's work counters and k_sym_reduce_w's arrival counter (kTicketWords)
+    // k_symv_dyn's work counters and the rank reductions' arrival counter (kTicketWords)
     MLFF_HIP(ctx, hipMalloc(&sp.ticket, kTicketWords * sizeof(unsigned long long)));
     MLFF_HIP(ctx, hipMemsetAsync(sp.ticket, 0, kTicketWords * sizeof(unsigned long long), s));
     if (ctx->world > 1) {
@@ -1363,123 +1342,117 @@ int sym_build(mlff_ctx *ctx, bool check_symmetry, bool *symmetric_out) {
   sp.ntiles = nt;
   sp.Np = Np;
   sp.nb = nb;
-  sp.tiles_per_rank = tpr;
-  sp.nwhole = nwhole;
-  sp.lsub = lsub;
-  sp.dyn = dyn;
-  // Generating role (k_symv_dyn<true>): only where the tiles come from the RBF points, which
-  // stay resident, and their dimension fits the role's registers.  The last n_gen whole tiles
-  // are evaluated instead of read; the share follows the two roles' measured rates
-  // (kSymStreamRate / kSymGenRate, common.h).  MLFF_SYM_GEN=0: off (every unit
-  // streamed on the old grid); MLFF_SYM_GEN_TILES=<n>: n generated whole tiles (clamped);
-  // MLFF_SYM_GEN_QUARTERS=0|1|2: the quarter units to either role / streamed / generated.
-  sp.gen = false;
-  sp.gsrc = SymGen{};
-  if (dyn > 0 && nt > 0 && !ctx->has_matrix && ctx->rbf.ready && ctx->rbf.d >= 1 &&
-      ctx->rbf.d <= kSymGenMaxD) {
-    bool on = true;
-    if (const char *e = std::getenv("MLFF_SYM_GEN")) on = std::atoi(e) != 0;
-    int64_t n_s = (int64_t)((double)nwhole * kSymStreamRate / (kSymStreamRate + kSymGenRate) + 0.5);
-    if (const char *e = std::getenv("MLFF_SYM_GEN_TILES"))
-      n_s = nwhole - std::min<int64_t>(nwhole, std::max<int64_t>(0, std::atoll(e)));
-    int qmode = 0;
-    if (const char *e = std::getenv("MLFF_SYM_GEN_QUARTERS")) {
-      const int v = std::atoi(e);
-      if (v >= 0 && v <= 2) qmode = v;
-    }
-    if (nwhole == nt && n_s == nwhole) on = false;                // nothing to generate
-    if (n_s == nwhole && qmode == 1) on = false;                  // every unit streamed
-    if (on) {
-      sp.gen = true;
-      sp.gsrc = SymGen{ctx->rbf.Xs, ctx->rbf.d, ctx->rbf.jitter, ctx->N, ctx->rows_per, ctx->blk,
-                       (int)n_s, qmode};
-    }
+  sp.tiles_per_rank = pl.tpr;
+  sp.nwhole = pl.nwhole;
+  sp.lsub = pl.lsub;
+  sp.dyn = pl.dyn;
+  sp.gen = pl.gen;
+  sp.gsrc = pl.gsrc;
+  sp.pq_ordered = kn.pq_ordered;
+  return MLFF_OK;
+}
+
+// the slot reductions' tables: split flags (k_sym_reduce), owned slots (k_sym_reduce_w) and
+// the flat load list (k_sym_reduce_wl)
+static int sym_slot_tables(mlff_ctx *ctx, const SymPlan &pl, const SymKnobs &kn) {
+  SymPack &sp = ctx->sym;
+  hipStream_t s = ctx->stream;
+  const int nb = pl.nb;
+  std::vector<unsigned char> split((size_t)nb * nb, 0);
+  sp.t_split = nb;
+  for (int64_t t = pl.nwhole; t < pl.nt; ++t) {
+    split[(size_t)pl.list[t].x * nb + pl.list[t].y] = 1;
+    sp.t_split = std::min<int64_t>(sp.t_split, pl.list[t].x);
   }
-  {
-    std::vector<unsigned char> split((size_t)nb * nb, 0);
-    sp.t_split = nb;
-    for (int64_t t = nwhole; t < nt; ++t) {
-      split[(size_t)list[t].x * nb + list[t].y] = 1;
-      sp.t_split = std::min<int64_t>(sp.t_split, list[t].x);
+  MLFF_HIP(ctx, hipMemcpyAsync(sp.split, split.data(), split.size(), hipMemcpyHostToDevice, s));
+  // owned slots per row block: row bi's slot t is this rank's when it stores tile
+  // (max(bi, t), min(bi, t)); rows of nb ascending entries, then nb counts
+  std::vector<int> own((size_t)nb * (nb + 1), 0);
+  for (int bi = 0; bi < nb; ++bi) {
+    int c = 0;
+    for (int t = 0; t < nb; ++t)
+      if (owner_host(std::max(bi, t), std::min(bi, t), pl.tpr) == ctx->rank)
+        own[(size_t)bi * nb + c++] = sym_own_entry(t, t > bi && split[(size_t)t * nb + bi]);
+    own[(size_t)nb * nb + bi] = c;
+  }
+  MLFF_HIP(ctx, hipMemcpyAsync(sp.own, own.data(), sizeof(int) * own.size(), hipMemcpyHostToDevice, s));
+  // the flat load list: each owned slot, a split slot followed by its planes; row blocks at a
+  // stride of the longest list (rounded to 64 entries)
+  std::vector<std::vector<int>> lists((size_t)nb);
+  sp.pmax = 0;
+  for (int bi = 0; bi < nb; ++bi) {
+    for (int j = 0; j < own[(size_t)nb * nb + bi]; ++j) {
+      const int e = own[(size_t)bi * nb + j];
+      for (int h = 0; h <= (sym_own_split(e) ? pl.nq : 0); ++h)
+        lists[bi].push_back(sym_plist_entry(sym_own_slot(e), h));
     }
-    MLFF_HIP(ctx, hipMemcpyAsync(sp.split, split.data(), split.size(), hipMemcpyHostToDevice, s));
-    // owned slots per row block (k_sym_reduce_w): row bi's slot t is this rank's when it
-    // stores tile (max(bi, t), min(bi, t)); rows of nb ascending entries, then nb counts
-    std::vector<int> own((size_t)nb * (nb + 1), 0);
-    for (int bi = 0; bi < nb; ++bi) {
-      int c = 0;
-      for (int t = 0; t < nb; ++t)
-        if (owner_host(std::max(bi, t), std::min(bi, t), tpr) == ctx->rank)
-          own[(size_t)bi * nb + c++] = t | (t > bi && split[(size_t)t * nb + bi] ? kOwnSplit : 0);
-      own[(size_t)nb * nb + bi] = c;
-    }
-    MLFF_HIP(ctx, hipMemcpyAsync(sp.own, own.data(), sizeof(int) * own.size(), hipMemcpyHostToDevice, s));
-    // the flat load list of k_sym_reduce_wl: each owned slot, a split slot followed by its planes;
-    // row blocks at a stride of the longest list (rounded to 64 entries)
-    std::vector<std::vector<int>> lists((size_t)nb);
-    sp.pmax = 0;
-    for (int bi = 0; bi < nb; ++bi) {
-      for (int j = 0; j < own[(size_t)nb * nb + bi]; ++j) {
-        const int e = own[(size_t)bi * nb + j];
-        const int t = e & (kOwnSplit - 1);
-        lists[bi].push_back(t);
-        if (e & kOwnSplit)
-          for (int h = 1; h <= nq; ++h) lists[bi].push_back(t | (h << 16));
-      }
-      sp.pmax = std::max(sp.pmax, (int)lists[bi].size());
-    }
-    sp.pstride = round_up(std::max(sp.pmax, 1), 64);
-    std::vector<int> plist((size_t)nb * (sp.pstride + 1), 0);
-    for (int bi = 0; bi < nb; ++bi) {
-      std::copy(lists[bi].begin(), lists[bi].end(), plist.begin() + (size_t)bi * sp.pstride);
-      plist[(size_t)nb * sp.pstride + bi] = (int)lists[bi].size();
-    }
-    if (sp.plist != nullptr) (void)hipFree(sp.plist);
-    sp.plist = nullptr;
-    const char *rl = std::getenv("MLFF_SYM_REDUCE_LIST");
-    if (ctx->world > 1 && (rl == nullptr || std::atoi(rl) != 0)) {
-      MLFF_HIP(ctx, hipMalloc(&sp.plist, sizeof(int) * plist.size()));
-      MLFF_HIP(ctx, hipMemcpyAsync(sp.plist, plist.data(), sizeof(int) * plist.size(),
-                                   hipMemcpyHostToDevice, s));
-    }
+    sp.pmax = std::max(sp.pmax, (int)lists[bi].size());
+  }
+  sp.pstride = round_up(std::max(sp.pmax, 1), 64);
+  std::vector<int> plist((size_t)nb * (sp.pstride + 1), 0);
+  for (int bi = 0; bi < nb; ++bi) {
+    std::copy(lists[bi].begin(), lists[bi].end(), plist.begin() + (size_t)bi * sp.pstride);
+    plist[(size_t)nb * sp.pstride + bi] = (int)lists[bi].size();
+  }
+  if (sp.plist != nullptr) (void)hipFree(sp.plist);
+  sp.plist = nullptr;
+  if (ctx->world > 1 && kn.reduce_list) {
+    MLFF_HIP(ctx, hipMalloc(&sp.plist, sizeof(int) * plist.size()));
+    MLFF_HIP(ctx, hipMemcpyAsync(sp.plist, plist.data(), sizeof(int) * plist.size(),
+                                 hipMemcpyHostToDevice, s));
+  }
+  MLFF_HIP(ctx, hipStreamSynchronize(s));  // the host vectors go out of scope
+  return MLFF_OK;
+}
+
+// the tiles: generated from the RBF points, or packed from the dense rows and, on request,
+// compared with their mirror
+static int sym_fill(mlff_ctx *ctx, const SymPlan &pl, bool check_symmetry, bool *symmetric_out) {
+  SymPack &sp = ctx->sym;
+  hipStream_t s = ctx->stream;
+  const int64_t nt = pl.nt;
+  if (symmetric_out) *symmetric_out = true;
+  if (nt == 0) return MLFF_OK;
+  MLFF_HIP(ctx, hipMemcpyAsync(sp.list, pl.list.data(), sizeof(int2) * nt, hipMemcpyHostToDevice, s));
+  if (!ctx->has_matrix && ctx->rbf.ready) {  // generated from the points (no dense rows)
+    hipLaunchKernelGGL(k_sym_gen_rbf, dim3((unsigned)nt), dim3(256), 0, s, sp.list, ctx->rbf.Xs,
+                       ctx->rbf.d, ctx->rbf.jitter, ctx->N, ctx->rows_per, ctx->blk, sp.tiles);
+    MLFF_HIP(ctx, hipGetLastError());
     MLFF_HIP(ctx, hipStreamSynchronize(s));
+    return MLFF_OK;
   }
   unsigned char *dtrans = nullptr;
   int *dflag = nullptr;
-  if (nt > 0) {
-    MLFF_HIP(ctx, hipMemcpyAsync(sp.list, list.data(), sizeof(int2) * nt, hipMemcpyHostToDevice, s));
-    MLFF_HIP(ctx, hipMalloc(&dtrans, nt));
-    MLFF_HIP(ctx, hipMalloc(&dflag, sizeof(int)));
-    MLFF_HIP(ctx, hipMemcpyAsync(dtrans, trans.data(), nt, hipMemcpyHostToDevice, s));
-    MLFF_HIP(ctx, hipMemsetAsync(dflag, 0, sizeof(int), s));
-    const int64_t rowbase = (int64_t)ctx->rank * ctx->blk;
-    const double *Ksrc = ctx->K;
-    const int64_t ldsrc = ctx->ld;
-    if (!ctx->has_matrix && ctx->rbf.ready) {  // generated from the points (no dense rows)
-      hipLaunchKernelGGL(k_sym_gen_rbf, dim3((unsigned)nt), dim3(256), 0, s, sp.list, ctx->rbf.Xs,
-                         ctx->rbf.d, ctx->rbf.jitter, ctx->N, ctx->rows_per, ctx->blk, sp.tiles);
-      check_symmetry = false;
-    } else {
-      hipLaunchKernelGGL(k_sym_pack<false>, dim3((unsigned)nt), dim3(256), 0, s, Ksrc, ldsrc, rowbase,
-                         ctx->blk, sp.list, dtrans, sp.tiles, dflag);
-    }
-    int mism = 0;
-    if (check_symmetry) {
-      // mirror read: every tile compared against rows J B + c (one rank holds all rows)
-      MLFF_HIP(ctx, hipMemsetAsync(dtrans, 1, nt, s));
-      hipLaunchKernelGGL(k_sym_pack<true>, dim3((unsigned)nt), dim3(256), 0, s, Ksrc, ldsrc, rowbase,
-                         ctx->blk, sp.list, dtrans, sp.tiles, dflag);
-      MLFF_HIP(ctx, hipMemcpyAsync(&mism, dflag, sizeof(int), hipMemcpyDeviceToHost, s));
-    }
-    MLFF_HIP(ctx, hipGetLastError());
-    MLFF_HIP(ctx, hipStreamSynchronize(s));
-    hipFree(dtrans);
-    hipFree(dflag);
-    if (symmetric_out) *symmetric_out = (mism == 0);
-  } else if (symmetric_out) {
-    *symmetric_out = true;
+  MLFF_HIP(ctx, hipMalloc(&dtrans, nt));
+  MLFF_HIP(ctx, hipMalloc(&dflag, sizeof(int)));
+  MLFF_HIP(ctx, hipMemcpyAsync(dtrans, pl.trans.data(), nt, hipMemcpyHostToDevice, s));
+  MLFF_HIP(ctx, hipMemsetAsync(dflag, 0, sizeof(int), s));
+  const int64_t rowbase = (int64_t)ctx->rank * ctx->blk;
+  hipLaunchKernelGGL(k_sym_pack<false>, dim3((unsigned)nt), dim3(256), 0, s, ctx->K, ctx->ld, rowbase,
+                     ctx->blk, sp.list, dtrans, sp.tiles, dflag);
+  int mism = 0;
+  if (check_symmetry) {
+    // mirror read: every tile compared against rows J B + c (one rank holds all rows)
+    MLFF_HIP(ctx, hipMemsetAsync(dtrans, 1, nt, s));
+    hipLaunchKernelGGL(k_sym_pack<true>, dim3((unsigned)nt), dim3(256), 0, s, ctx->K, ctx->ld, rowbase,
+                       ctx->blk, sp.list, dtrans, sp.tiles, dflag);
+    MLFF_HIP(ctx, hipMemcpyAsync(&mism, dflag, sizeof(int), hipMemcpyDeviceToHost, s));
   }
-  sp.ready = true;
+  MLFF_HIP(ctx, hipGetLastError());
+  MLFF_HIP(ctx, hipStreamSynchronize(s));
+  (void)hipFree(dtrans);
+  (void)hipFree(dflag);
+  if (symmetric_out) *symmetric_out = (mism == 0);
+  return MLFF_OK;
+}
+
+int sym_build(mlff_ctx *ctx, bool check_symmetry, bool *symmetric_out) {
+  const SymKnobs kn = sym_knobs();
+  const SymPlan pl = sym_plan(ctx, kn);
+  if (int rc = sym_alloc(ctx, pl, kn); rc != MLFF_OK) return rc;
+  if (int rc = sym_slot_tables(ctx, pl, kn); rc != MLFF_OK) return rc;
+  if (int rc = sym_fill(ctx, pl, check_symmetry, symmetric_out); rc != MLFF_OK) return rc;
+  ctx->sym.ready = true;
   return MLFF_OK;
 }
 
@@ -1488,22 +1461,7 @@ void sym_free(SymPack &sp) {
                   (void *)sp.Pq, (void *)sp.split, (void *)sp.ticket, (void *)sp.own,
                   (void *)sp.plist})
     if (p) (void)hipFree(p);
-  sp.own = nullptr;
-  sp.plist = nullptr;
-  sp.pmax = 0;
-  sp.Pq = nullptr;
-  sp.split = nullptr;
-  sp.ticket = nullptr;
-  sp.tiles = nullptr;
-  sp.list = nullptr;
-  sp.P = nullptr;
-  sp.yg = nullptr;
-  sp.yr = nullptr;
-  sp.ntiles = 0;
-  sp.pq_planes = 0;
-  sp.gen = false;
-  sp.gsrc = SymGen{};
-  sp.ready = false;
+  sp = SymPack{};
 }
 
 }  // namespace mlff

@@ -193,6 +193,22 @@ def test_sharded_sym_reduce_list_bitwise(world, precon, n, lsub, monkeypatch):
         np.testing.assert_array_equal(a["y"], b["y"])
 
 
+@pytest.mark.parametrize("world", [3, 8])
+def test_sharded_pq_arrival_ordered_bitwise(world, monkeypatch):
+    """k_sym_reduce_wl's last-arriver publish with the release / acquire arrival
+    (MLFF_SYM_PQ_ORDERED=1, read at the operator's build) against its default write-through
+    arrival: one helper, the same sums in the same order, so the same iterates."""
+    n = 1003
+    out = {}
+    for ordered in ("1", "0"):
+        monkeypatch.setenv("MLFF_SYM_PQ_ORDERED", ordered)
+        out[ordered] = run_ranks(world, lambda r, w, key: solve_case(r, w, key, n, "nystrom"))
+    for a, b in zip(out["1"], out["0"]):
+        assert a["iters"] == b["iters"] and a["info"] == b["info"] == 0
+        np.testing.assert_array_equal(a["trace"], b["trace"])
+        np.testing.assert_array_equal(a["x"], b["x"])
+
+
 @pytest.mark.timeout(600)
 @pytest.mark.parametrize("world,precon,n", [(2, "nystrom", 1003), (3, "pivchol", 1003),
                                             (8, "nystrom", 1003), (2, "nystrom", 9000),

@@ -184,3 +184,37 @@ def test_symtile_fused_p_update_bitwise(sg, n, k, forms, monkeypatch):
     assert a.info == c.info and a.iters == c.iters
     np.testing.assert_array_equal(a.trace, c.trace)
     np.testing.assert_array_equal(a.x, c.x)
+
+
+def _sched_outputs(sg, n, monkeypatch, sched, gen):
+    """Mat-vecs of the RBF operator of size n under one launch schedule (None: the default)."""
+    for key, val in (("MLFF_SYM_SCHED", sched), ("MLFF_SYM_GEN", gen)):
+        if val is None:
+            monkeypatch.delenv(key, raising=False)
+        else:
+            monkeypatch.setenv(key, val)
+    rng = np.random.default_rng(11)
+    X, v = rng.random((n, 3)), rng.standard_normal(n)
+    e0, e1 = np.zeros(n), np.zeros(n)
+    e0[0] = e1[n - 1] = 1.0  # columns of the operator: entry bits, not only sums
+    with sg.KernelSolver(n) as s:
+        s.gen_rbf(X, 0.3, jitter=1e-9)
+        s.set_operator(1.0, 1e-3)
+        assert s.storage_info()[0] == "sym"
+        # twice each: the second application runs on counters reset by the first
+        return [s.matvec(x) for x in (v, e0, e1) for _ in range(2)]
+
+
+@pytest.mark.parametrize("gen", ["0", None])
+@pytest.mark.parametrize("n", [700, 16900])
+def test_symtile_static_schedule_bitwise(sg, n, gen, monkeypatch):
+    """k_symv_tiles (MLFF_SYM_SCHED=static) and k_symv_dyn run one tile body, so the two
+    schedules write the same bits -- all streamed (MLFF_SYM_GEN=0) and with the default
+    generating role.  n = 700: 3 tiles, all quarters, padded rows and columns, one
+    diagonal-only row block; n = 16900: 512 whole tiles + 83 split, both unit kinds and the
+    tail."""
+    static = _sched_outputs(sg, n, monkeypatch, "static", gen)
+    default = _sched_outputs(sg, n, monkeypatch, None, gen)
+    assert len(static) == len(default) == 6
+    for a, b in zip(static, default):
+        assert np.array_equal(a, b)
