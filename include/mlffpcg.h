@@ -20,6 +20,8 @@
  *       src/sGDML/sgdml/utils/desc.py:292-358                        -> mlff_sgdml_descriptors
  *   GDMLPredict energies on the training set (for _recov_int_const)
  *       src/sGDML/sgdml/predict.py:172-220; train.py:972-1119        -> mlff_sgdml_energies
+ *   GDMLPredict.__init__ / predict (E, F at new geometries)
+ *       src/sGDML/sgdml/predict.py:237-384, 997-1110                 -> mlff_predict_set_model + mlff_predict
  *   tools.utils.create_kernel_mat (synthetic RBF)
  *       src/tools/utils.py:173-187                                   -> mlff_gen_rbf
  *   set dense K from the caller (K_hat in custom_cg_solver)
@@ -226,6 +228,30 @@ int mlff_sgdml_descriptors(const double *R, int64_t M, int n_atoms, double *R_de
  * matrix-free operator data (mlff_sgdml_operator or mlff_assemble_sgdml). */
 int mlff_sgdml_energies(mlff_ctx *ctx, const double *alphas, double *E_out, int64_t *i0_out,
                         int64_t *ni_out);
+
+/* Hold a trained sGDML model for prediction: GDMLPredict.__init__ (predict.py:294-362), which
+ * forms R_desc_perms / R_d_desc_alpha_perms from the model's R_desc (passed here as M x D, the
+ * model file stores D x M), R_d_desc_alpha (M x D), perms (n_perms x n_atoms; the descriptor
+ * permutations are derived as Desc.perm does, desc.py:360-389), sig, std and the integration
+ * constant c.  One-rank context created with n_global = 3 n_atoms M (MLFF_ERR_ARG otherwise);
+ * independent of any operator or matrix of the context; replaces an earlier model.  The pair
+ * stage runs in the tile form for D <= 288 and in the stream form otherwise;
+ * MLFF_PRED_FORM=tile|stream (tile on a larger D: MLFF_ERR_ARG) and MLFF_PRED_SLAB=<queries
+ * per pass> are read here.  No lattice, no cut-off, no alphas_E (use_E_cstr models). */
+int mlff_predict_set_model(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc_alpha,
+                           int64_t M, int n_atoms, const int32_t *perms, int n_perms, double sig,
+                           double std, double c);
+/* GDMLPredict.predict(R) (predict.py:997-1110; worker _predict_wkr, :72-234; descriptors
+ * Desc.from_R, desc.py:203-358; vec_dot_d_desc, desc.py:408-428): R (Q x n_atoms x 3) ->
+ * E_out (Q) = std E + c, F_out (Q x 3 n_atoms) = std F.  Every query's result has the same bits
+ * whatever the batch it arrives in.  MLFF_ERR_STATE before a model is set; Q = 0 is MLFF_OK. */
+int mlff_predict(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F_out);
+/* The prediction set up by mlff_predict_set_model: form_out 0 tile / 1 stream, slab_out the
+ * queries per pass, and the algorithmic work of one query -- flops of the pair stage
+ * (M n_perms (9 D + 10)) and bytes of the R_desc_perms / R_d_desc_alpha_perms stream
+ * (predict.py:174-175).  No reference counterpart (measurement). */
+int mlff_predict_info(mlff_ctx *ctx, int *form_out, int64_t *slab_out, double *flops_per_query_out,
+                      double *bytes_per_query_out);
 
 int mlff_set_operator(mlff_ctx *ctx, double sigma_K, double lam);
 /* y_local = A v_global (v_global has N entries).  Collective over the ranks

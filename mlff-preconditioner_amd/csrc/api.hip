@@ -1333,6 +1333,7 @@ int mlff_ctx_destroy(mlff_ctx *ctx) {
   ctx->scratch_chunks.clear();
   sym_free(ctx->sym);
   mf_free(ctx->mf);
+  pred_free(ctx->pred);
   rbf_free(ctx);
   if (ctx->h_st) hipHostFree(ctx->h_st);
   for (hipEvent_t e : ctx->timing.ev) hipEventDestroy(e);
@@ -1622,6 +1623,51 @@ int mlff_sgdml_energies(mlff_ctx *ctx, const double *alphas, double *E_out, int6
   }
   if (i0_out) *i0_out = mf.i0;
   if (ni_out) *ni_out = mf.ni;
+  return MLFF_OK;
+  MLFF_API_END(ctx)
+}
+
+int mlff_predict_set_model(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc_alpha,
+                           int64_t M, int n_atoms, const int32_t *perms, int n_perms, double sig,
+                           double std, double c) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  if (ctx->world > 1) return set_error(ctx, MLFF_ERR_ARG, "predict: runs on a one-rank context");
+  if (R_desc == nullptr || R_d_desc_alpha == nullptr || perms == nullptr)
+    return set_error(ctx, MLFF_ERR_ARG, "predict: null pointer");
+  if (n_atoms < 2 || M < 1 || n_perms < 1 || n_perms > 1024)
+    return set_error(ctx, MLFF_ERR_ARG, "predict: bad sizes");
+  if (3 * (int64_t)n_atoms * M != ctx->N)
+    return set_error(ctx, MLFF_ERR_ARG, "predict: N != 3 * n_atoms * M");
+  if (!(sig > 0.0)) return set_error(ctx, MLFF_ERR_ARG, "predict: sig must be > 0");
+  return pred_set_model(ctx, R_desc, R_d_desc_alpha, M, n_atoms, perms, n_perms, sig, std, c);
+  MLFF_API_END(ctx)
+}
+
+int mlff_predict(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  if (ctx->world > 1) return set_error(ctx, MLFF_ERR_ARG, "predict: runs on a one-rank context");
+  if (!ctx->pred.ready) return set_error(ctx, MLFF_ERR_STATE, "predict: no model set (mlff_predict_set_model)");
+  if (Q < 0) return set_error(ctx, MLFF_ERR_ARG, "predict: Q < 0");
+  if (Q == 0) return MLFF_OK;
+  if (R == nullptr || E_out == nullptr || F_out == nullptr)
+    return set_error(ctx, MLFF_ERR_ARG, "predict: null pointer");
+  return pred_run(ctx, R, Q, E_out, F_out);
+  MLFF_API_END(ctx)
+}
+
+int mlff_predict_info(mlff_ctx *ctx, int *form_out, int64_t *slab_out, double *flops_per_query_out,
+                      double *bytes_per_query_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  if (!ctx->pred.ready) return set_error(ctx, MLFF_ERR_STATE, "predict: no model set (mlff_predict_set_model)");
+  double fl = 0.0, by = 0.0;
+  pred_work(ctx->pred, &fl, &by);
+  if (form_out) *form_out = ctx->pred.form;
+  if (slab_out) *slab_out = ctx->pred.slab;
+  if (flops_per_query_out) *flops_per_query_out = fl;
+  if (bytes_per_query_out) *bytes_per_query_out = by;
   return MLFF_OK;
   MLFF_API_END(ctx)
 }

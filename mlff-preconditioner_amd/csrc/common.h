@@ -167,6 +167,28 @@ struct MfData {
   double *eterm = nullptr;  // ni x (M n_perms): a_ijp w_ijp of the last application
 };
 
+// Trained sGDML model held for prediction at new geometries (kernels_predict.hip): the
+// permuted training descriptors / Jacobian-coefficient products, the form of the pair stage and
+// the per-slab work buffers.  Independent of the operator (MfData) and of the matrix.
+struct PredData {
+  bool ready = false;
+  int64_t M = 0, D = 0, MP = 0;
+  int n = 0, n_perms = 0;
+  double sig = 0.0, std = 1.0, c = 0.0;
+  int form = 0;            // 0 tile (k_pr_pair), 1 stream (k_pr_stream)
+  int S = 1;               // chunks of the (j, p) range: fixed by MP and the form
+  int G = 1;               // queries per workgroup of the pair stage
+  int64_t slab = 0;        // queries per pass (bounds part)
+  int64_t PS = 0, ecol = 0;  // row stride of part, column of the energy partial
+  double *Rt = nullptr, *Zt = nullptr;      // MP x D
+  double *Rq = nullptr;                     // slab x n x 3 query geometries
+  double *Rdq = nullptr, *Rddq = nullptr;   // slab x D, slab x D x 3
+  double *part = nullptr;                   // S x slab x PS chunk partials
+  double *Fd = nullptr;                     // slab x D
+  double *EF = nullptr;                     // results of a slab: E (slab) then F (slab x 3 n)
+  double *h_in = nullptr, *h_out = nullptr; // pinned staging of Rq and EF: one copy each way
+};
+
 // Synthetic RBF kernel source (tools/utils.py:173-187): the points, scaled by 1 / length
 // scale, stay on the device and every consumer evaluates K from them -- the symmetric
 // tiles are generated directly, columns / the diagonal / requested rows on demand -- so no
@@ -256,6 +278,25 @@ __device__ __forceinline__ double fused_p(double pold, double z, double beta, bo
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
+  return v;
+}
+
+// xor-partner sum over the L lanes of a point with DPP moves (VALU, no LDS round trip):
+// quad_perm [1,0,3,2] and [2,3,0,1] pair lanes 1 and 2 apart, row_half_mirror pairs every lane
+// of a quad with one of the other quad of its 8 (each step adds a commutative pair: every lane
+// of the group ends with the same bits)
+template <int CTRL>
+__device__ __forceinline__ double dpp_f64(double v) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
+  return __hiloint2double(hi, lo);
+}
+template <int L>
+__device__ __forceinline__ double group_sum(double v) {
+  static_assert(L == 1 || L == 2 || L == 4 || L == 8, "DPP butterfly for L <= 8");
+  if (L >= 2) v += dpp_f64<0xB1>(v);   // quad_perm(1, 0, 3, 2)
+  if (L >= 4) v += dpp_f64<0x4E>(v);   // quad_perm(2, 3, 0, 1)
+  if (L >= 8) v += dpp_f64<0x141>(v);  // row_half_mirror
   return v;
 }
 
@@ -386,6 +427,7 @@ struct mlff_ctx {
   mlff::SymPack sym;
   mlff::MfData mf;                  // matrix-free sGDML operator (optional)
   mlff::RbfData rbf;                // synthetic RBF kernel from its points (optional)
+  mlff::PredData pred;              // trained model for prediction (optional)
 
   // CG vectors.  local: blk entries; p_full / xg: ld entries (rank blocks)
   double *x = nullptr, *r = nullptr, *z = nullptr, *q = nullptr, *b = nullptr;
@@ -811,6 +853,17 @@ double mf_seconds(const mlff_ctx *ctx);
 void mf_free(MfData &mf);
 int desc_perm_tables(mlff_ctx *ctx, const int32_t *perms, int n, int n_perms,
                      std::vector<int32_t> &Pt, std::vector<int32_t> &piinv);
+
+// ---- prediction at new geometries (kernels_predict.hip) ----------------------
+// hold a trained model (replaces the context's earlier one); MLFF_PRED_FORM / MLFF_PRED_SLAB
+// are read here
+int pred_set_model(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc_alpha, int64_t M,
+                   int n_atoms, const int32_t *perms, int n_perms, double sig, double std, double c);
+// E (Q), F (Q x 3 n) of the Q host geometries R, in slabs of pred.slab queries
+int pred_run(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F_out);
+bool pred_tile_supported(int64_t D);
+void pred_work(const PredData &pd, double *flops_per_query, double *bytes_per_query);
+void pred_free(PredData &pd);
 
 // ---- operator access for the builds (api.hip) --------------------------------
 // require the operator and resolve its storage (builds the tiles if they are to be used)

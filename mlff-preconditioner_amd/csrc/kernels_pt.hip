@@ -49,24 +49,7 @@ struct PtArgs {
   double *part;      // S x ni x DP
 };
 
-// xor-partner sum over the L lanes of a point with DPP moves (VALU, no LDS round trip):
-// quad_perm [1,0,3,2] and [2,3,0,1] pair lanes 1 and 2 apart, row_half_mirror pairs every lane
-// of a quad with one of the other quad of its 8 (each step adds a commutative pair: every lane
-// of the group ends with the same bits)
-template <int CTRL>
-__device__ __forceinline__ double dpp_f64(double v) {
-  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xF, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xF, 0xF, false);
-  return __hiloint2double(hi, lo);
-}
-template <int L>
-__device__ __forceinline__ double group_sum(double v) {
-  static_assert(L == 1 || L == 2 || L == 4 || L == 8, "DPP butterfly for L <= 8");
-  if (L >= 2) v += dpp_f64<0xB1>(v);   // quad_perm(1, 0, 3, 2)
-  if (L >= 4) v += dpp_f64<0x4E>(v);   // quad_perm(2, 3, 0, 1)
-  if (L >= 8) v += dpp_f64<0x141>(v);  // row_half_mirror
-  return v;
-}
+// (dpp_f64 / group_sum, the DPP butterfly over the L lanes of a point: common.h)
 
 // rows of Rt / Zt per LDS tile: 32, fewer for long descriptors (<= 18 KB per array)
 constexpr int pt_tile_rows(int DP) { return DP <= 72 ? 32 : DP <= 144 ? 16 : 8; }

@@ -9,6 +9,11 @@ with the solve on the MI355X: label vector y = F / std(F) (:837-845), lambda = 1
 dict has the reference model's keys and meanings, so `store_model` (train_models.py
 :127-154) writes the same `.npz` that the reference's analysis scripts read.
 
+`test_errors(model, R, F, E)` is the reference's test step (cli.py:855-865, 1217-1245): the
+model's energies and forces at held-out geometries, predicted on the GPU by
+`sgdml_amd.predict.GDMLPredict`, and their mean absolute / root mean square errors, which it
+can write into the model's `f_err` / `e_err` / `n_test` fields.
+
 Not covered (out of the solve path): symmetry compression (`use_cprsn`),
 energy constraints (`use_E_cstr`), periodic lattices, the 'analytic' solver.
 """
@@ -129,6 +134,54 @@ def recov_int_const(E_pred: np.ndarray, E_ref: np.ndarray):
     if np.abs(e_fact - 1) > 1e-1:
         return None
     return np.sum(E_ref - E_pred) / E_ref.shape[0]
+
+
+def prediction_errors(E_pred, F_pred, F, E=None) -> dict:
+    """The error figures of the reference's test step from predictions (cli.py:855-865
+    `_online_err` over one batch, :1232-1243): per force component mae = sum |err| / (3 n) / Q
+    and rmse = sqrt(sum err^2 / (3 n) / Q); the same per energy when E is given."""
+    F_pred = np.asarray(F_pred, dtype=np.float64)
+    Q = F_pred.shape[0]
+    if Q < 1:
+        raise ValueError("test_errors needs at least one geometry")
+    F_pred = F_pred.reshape(Q, -1)
+    F = np.asarray(F, dtype=np.float64).reshape(Q, -1)
+    if F.shape != F_pred.shape:
+        raise ValueError(f"F must match the predictions' shape {F_pred.shape}, got {F.shape}")
+
+    def err(d, size):
+        d = np.abs(d)
+        return {"mae": float(np.sum(d) / size / Q), "rmse": float(np.sqrt(np.sum(d ** 2) / size / Q))}
+
+    out = {"f_err": err(F - F_pred, F.shape[1]), "e_err": None, "n_test": Q}
+    if E is not None:
+        E = np.squeeze(np.asarray(E, dtype=np.float64)).reshape(-1)
+        E_pred = np.asarray(E_pred, dtype=np.float64).reshape(-1)
+        if E.shape != (Q,) or E_pred.shape != (Q,):
+            raise ValueError(f"E must have {Q} entries")
+        out["e_err"] = err(E - E_pred, 1)
+    return out
+
+
+def test_errors(model, R, F, E=None, device=None, devices=None, update=False) -> dict:
+    """The reference's test step (cli.py:1217-1245) on the GPU: predict at the geometries R
+    and return {"f_err": {"mae", "rmse"}, "e_err": {...} or None (no E), "n_test": Q}.
+    update=True writes them into the model dict (`f_err`, `n_test`, and `e_err` when E is
+    given), the fields create_model leaves at nan / 0."""
+    from .predict import GDMLPredict
+
+    with GDMLPredict(model, device=device, devices=devices) as gdml:
+        E_pred, F_pred = gdml.predict(R)
+    out = prediction_errors(E_pred, F_pred, F, E)
+    if update:
+        model["f_err"] = dict(out["f_err"])
+        model["n_test"] = out["n_test"]
+        if out["e_err"] is not None:
+            model["e_err"] = dict(out["e_err"])
+    return out
+
+
+test_errors.__test__ = False  # not a pytest test (the name is the reference step's)
 
 
 class _ModelFactory:

@@ -1,0 +1,224 @@
+"""GDMLPredict: energies and forces of a trained sGDML model at new geometries, on the MI355X.
+
+Drop-in for the reference's `sgdml.predict.GDMLPredict` (src/sGDML/sgdml/predict.py:237-384,
+997-1110) for models without lattice, cut-off or energy constraints:
+
+    with GDMLPredict("model.npz") as gdml:      # or a model dict / an open np.load result
+        E, F = gdml.predict(R)                  # R: Q x 3n, Q x n x 3, 3n or n x 3
+
+The model arrays go to the device once (`mlff_predict_set_model`); every `predict` call sends
+the geometries and gets E (Q,) and F (Q, 3n) back (`mlff_predict`, csrc/kernels_predict.hip).
+A query's result has the same bits whatever batch it is part of, so splitting a batch over
+`devices=[...]` (contiguous blocks, one context and one thread per entry) changes nothing.
+"""
+from __future__ import annotations
+
+import os
+import threading
+
+import numpy as np
+
+from .sharded import _Worker
+from .solver import KernelSolver
+
+# queries per workgroup of the pair stage (csrc/kernels_predict.hip: kPrThreads / L of the
+# variant that covers D; kPrQB of the stream form)
+STREAM_QUERY_BLOCK = 4
+TILE_MAX_D = 288
+
+
+def tile_queries_per_workgroup(D: int) -> int:
+    """G of the tile form for descriptor length D (k_pr_pair<L, DL>: 128 / L queries)."""
+    for L, DL in ((2, 18), (4, 18), (4, 28), (8, 28), (8, 36)):
+        if D <= L * DL:
+            return 128 // L
+    raise ValueError(f"the tile form covers D <= {TILE_MAX_D}, got {D}")
+
+
+def _scalar(v, name):
+    a = np.asarray(v)
+    if a.size != 1:
+        raise ValueError(f"model['{name}'] must be a scalar, got shape {a.shape}")
+    return float(a.reshape(()))
+
+
+def _has(model, key):
+    files = getattr(model, "files", None)
+    return key in files if files is not None else key in model
+
+
+def load_model_arrays(model) -> dict:
+    """The arrays the predictor needs from a model dict, an open `np.load` result or the path
+    of a `.npz` (written by `store_model` or by the reference): sig, std, c, R_desc (stored
+    D x M, returned M x D), R_d_desc_alpha (M x D), perms (n_perms x n), z.  Scalars may be
+    0-d arrays.  Only these keys are read, so pickled entries of the file are never loaded."""
+    opened = None
+    if isinstance(model, (str, os.PathLike)):
+        opened = model = np.load(model, allow_pickle=False)
+    try:
+        if _has(model, "type"):
+            t = np.asarray(model["type"]).reshape(-1)[0]
+            if t not in ("m", b"m"):
+                raise ValueError("the provided data structure is not a model (type != 'm')")
+        if _has(model, "lattice"):
+            raise NotImplementedError("models with a periodic lattice are not supported")
+        if _has(model, "alphas_E"):
+            raise NotImplementedError("models with energy constraints (alphas_E) are not supported")
+        if _has(model, "interact_cut_off"):
+            try:
+                cut = model["interact_cut_off"]
+            except ValueError:  # a pickled None in a .npz opened without pickle support
+                cut = None
+            if cut is not None and np.asarray(cut).dtype != object:
+                raise NotImplementedError("models with an interaction cut-off are not supported")
+        for key in ("sig", "c", "R_desc", "R_d_desc_alpha", "perms", "z"):
+            if not _has(model, key):
+                raise ValueError(f"model has no '{key}'")
+        z = np.asarray(model["z"]).reshape(-1)
+        n = z.size
+        D = n * (n - 1) // 2
+        perms = np.ascontiguousarray(np.atleast_2d(np.asarray(model["perms"])), dtype=np.int32)
+        R_desc = np.asarray(model["R_desc"], dtype=np.float64)
+        Rda = np.asarray(model["R_d_desc_alpha"], dtype=np.float64)
+        if n < 2:
+            raise ValueError("model['z'] must list at least two atoms")
+        if perms.ndim != 2 or perms.shape[1] != n:
+            raise ValueError(f"model['perms'] must be n_perms x {n}, got {perms.shape}")
+        if R_desc.ndim != 2 or R_desc.shape[0] != D:
+            raise ValueError(f"model['R_desc'] must be {D} x M (D = n (n - 1) / 2), got {R_desc.shape}")
+        M = R_desc.shape[1]
+        if M < 1 or Rda.shape != (M, D):
+            raise ValueError(f"model['R_d_desc_alpha'] must be {M} x {D}, got {Rda.shape}")
+        if not np.array_equal(np.sort(perms, axis=1), np.broadcast_to(np.arange(n), perms.shape)):
+            raise ValueError("model['perms']: every row must be a permutation of the atoms")
+        return {
+            "sig": _scalar(model["sig"], "sig"),
+            "std": _scalar(model["std"], "std") if _has(model, "std") else 1.0,
+            "c": _scalar(model["c"], "c"),
+            "R_desc": np.ascontiguousarray(R_desc.T),
+            "R_d_desc_alpha": np.ascontiguousarray(Rda),
+            "perms": perms,
+            "z": z.copy(),
+        }
+    finally:
+        if opened is not None:
+            opened.close()
+
+
+def normalize_geometries(R, n_atoms: int) -> np.ndarray:
+    """R as Q x 3n, Q x n x 3, or one geometry 3n / n x 3  ->  contiguous Q x n x 3."""
+    R = np.asarray(R, dtype=np.float64)
+    n3 = 3 * n_atoms
+    if R.ndim == 1 and R.size == n3:
+        R = R.reshape(1, n_atoms, 3)
+    elif R.ndim == 2 and R.shape == (n_atoms, 3):
+        R = R.reshape(1, n_atoms, 3)
+    elif R.ndim == 2 and R.shape[1] == n3:
+        R = R.reshape(R.shape[0], n_atoms, 3)
+    elif R.ndim == 3 and R.shape[1:] == (n_atoms, 3):
+        pass
+    else:
+        raise ValueError(f"R must be Q x {n3}, Q x {n_atoms} x 3, {n3} or {n_atoms} x 3; got {R.shape}")
+    return np.ascontiguousarray(R)
+
+
+def split_blocks(Q: int, parts: int) -> list[tuple[int, int]]:
+    """Contiguous blocks [a, b) of Q queries for `parts` workers (blocks may be empty)."""
+    per = -(-Q // parts) if Q > 0 else 0
+    return [(min(r * per, Q), min((r + 1) * per, Q)) for r in range(parts)]
+
+
+class GDMLPredict:
+    def __init__(self, model, device: int | None = None, devices=None):
+        arrs = load_model_arrays(model)
+        self.n_atoms = arrs["z"].size
+        self.n_train = arrs["R_desc"].shape[0]
+        self.n_perms = arrs["perms"].shape[0]
+        self.sig, self.std, self.c = arrs["sig"], arrs["std"], arrs["c"]
+        self._lock = threading.Lock()
+        self._workers = None
+        self._engines: list[KernelSolver] = []
+        n_global = 3 * self.n_atoms * self.n_train
+
+        def make(dev):
+            s = KernelSolver(n_global, device=dev)
+            try:
+                s.predict_set_model(arrs["R_desc"], arrs["R_d_desc_alpha"], arrs["perms"],
+                                    self.sig, self.std, self.c)
+            except BaseException:
+                s.close()
+                raise
+            return s
+
+        if devices is None:
+            self._engines = [make(device)]
+        else:
+            devices = [int(d) for d in devices]
+            if not devices:
+                raise ValueError("devices must name at least one device")
+            self._workers = [_Worker(f"mlff-predict{r}-dev{d}") for r, d in enumerate(devices)]
+            created: list[KernelSolver] = []
+
+            def make_on(r):
+                s = make(devices[r])
+                created.append(s)
+                return s
+
+            try:
+                self._engines = self._all(make_on)
+            except BaseException:
+                self._engines = created  # those that were set up: released by close()
+                self.close()
+                raise
+        form, slab, flops, nbytes = self._engines[0].predict_info()
+        self.form, self.slab = form, slab
+        self.flops_per_query, self.bytes_per_query = flops, nbytes
+
+    def _all(self, fn):
+        boxes, events = [], []
+        for r, w in enumerate(self._workers):
+            box, done = {}, threading.Event()
+            w.q.put((lambda r=r: fn(r), box, done))
+            boxes.append(box)
+            events.append(done)
+        for e in events:
+            e.wait()
+        for b in boxes:
+            if "error" in b:
+                raise b["error"]
+        return [b.get("value") for b in boxes]
+
+    def predict(self, R) -> tuple[np.ndarray, np.ndarray]:
+        """GDMLPredict.predict (predict.py:997-1110): E (Q,), F (Q, 3 n_atoms)."""
+        if not self._engines:
+            raise RuntimeError("GDMLPredict is closed")
+        R = normalize_geometries(R, self.n_atoms)
+        Q = R.shape[0]
+        if self._workers is None:
+            return self._engines[0].predict(R)
+        blocks = split_blocks(Q, len(self._engines))
+        parts = self._all(lambda r: self._engines[r].predict(R[blocks[r][0]:blocks[r][1]]))
+        return (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]))
+
+    def close(self):
+        """Release the device contexts and stop the workers (idempotent)."""
+        with self._lock:
+            engines, self._engines = self._engines, []
+            workers, self._workers = self._workers, None
+        for s in engines:
+            if s is not None:
+                s.close()
+        for w in workers or []:
+            w.q.put(None)
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass

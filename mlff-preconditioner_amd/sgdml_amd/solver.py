@@ -169,6 +169,48 @@ class KernelSolver:
                    ctypes.byref(ni))
         return i0.value, E[: ni.value].copy()
 
+    # -------------------------------------------------------------- prediction
+    def predict_set_model(self, R_desc: np.ndarray, R_d_desc_alpha: np.ndarray, perms: np.ndarray,
+                          sig: float, std: float = 1.0, c: float = 0.0):
+        """Hold a trained sGDML model for `predict` (GDMLPredict.__init__, predict.py:294-362):
+        R_desc and R_d_desc_alpha as M x D, perms n_perms x n_atoms.  The solver's N must be
+        3 n_atoms M; independent of any operator set on it."""
+        R_desc = np.ascontiguousarray(R_desc, dtype=np.float64)
+        Rda = np.ascontiguousarray(R_d_desc_alpha, dtype=np.float64)
+        perms = np.ascontiguousarray(np.atleast_2d(perms), dtype=np.int32)
+        if R_desc.ndim != 2:
+            raise ValueError("R_desc must be M x D")
+        M, D = R_desc.shape
+        n_atoms = perms.shape[1]
+        if Rda.shape != (M, D) or D != n_atoms * (n_atoms - 1) // 2:
+            raise ValueError("R_desc / R_d_desc_alpha / perms shapes do not match")
+        self._call("mlff_predict_set_model", nat.dptr(R_desc), nat.dptr(Rda), int(M), int(n_atoms),
+                   nat.i32ptr(perms), int(perms.shape[0]), float(sig), float(std), float(c))
+        self._pred_n_atoms = n_atoms
+
+    def predict(self, R: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        """E (Q,), F (Q, 3 n_atoms) of the geometries R (Q x n_atoms x 3) with the model set by
+        `predict_set_model` (GDMLPredict.predict, predict.py:997-1110)."""
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        n = getattr(self, "_pred_n_atoms", None)
+        if n is not None and (R.ndim != 3 or R.shape[1:] != (n, 3)):
+            raise ValueError(f"R must be Q x {n} x 3, got {R.shape}")
+        if n is None and (R.ndim != 3 or R.shape[2] != 3):
+            raise ValueError("R must be Q x n_atoms x 3")
+        Q, n = R.shape[0], R.shape[1]
+        E = np.empty(Q)
+        F = np.empty((Q, 3 * n))
+        self._call("mlff_predict", nat.dptr(R), int(Q), nat.dptr(E), nat.dptr(F))
+        return E, F
+
+    def predict_info(self) -> tuple[str, int, float, float]:
+        """(form 'tile' | 'stream', queries per pass, flops and streamed bytes of one query)."""
+        form, slab = ctypes.c_int(), ctypes.c_int64()
+        fl, by = ctypes.c_double(), ctypes.c_double()
+        self._call("mlff_predict_info", ctypes.byref(form), ctypes.byref(slab), ctypes.byref(fl),
+                   ctypes.byref(by))
+        return {0: "tile", 1: "stream"}[form.value], slab.value, fl.value, by.value
+
     def set_operator(self, sigma_K: float, lam: float):
         self._call("mlff_set_operator", float(sigma_K), float(lam))
 
