@@ -22,6 +22,8 @@
  *       src/sGDML/sgdml/predict.py:172-220; train.py:972-1119        -> mlff_sgdml_energies
  *   GDMLPredict.__init__ / predict (E, F at new geometries)
  *       src/sGDML/sgdml/predict.py:237-384, 997-1110                 -> mlff_predict_set_model + mlff_predict
+ *   Analytic.solve (closed form: cho_factor / cho_solve of -K + 1e-10 I)
+ *       src/sGDML/sgdml/solvers/analytic.py:47-208                   -> mlff_dense_cho_solve
  *   tools.utils.create_kernel_mat (synthetic RBF)
  *       src/tools/utils.py:173-187                                   -> mlff_gen_rbf
  *   set dense K from the caller (K_hat in custom_cg_solver)
@@ -192,6 +194,29 @@ int mlff_spectrum(mlff_ctx *ctx, int preconditioned, double *eig_out);
 int mlff_test_gemm(mlff_ctx *ctx, int ta, int tb, int64_t M, int64_t N, int64_t K, double alpha,
                    const double *A, int64_t lda, const double *B, int64_t ldb, double beta,
                    double *C, int64_t ldc, int splits);
+/* Closed-form solve, Analytic.solve (src/sGDML/sgdml/solvers/analytic.py:129-153: K[diag] -=
+ * 1e-10; cho_factor(-K); alphas = -cho_solve(...)): x_out (N) = (sigma_K K + shift I)^-1 b with
+ * the context's dense rows (mlff_set_matrix_host / mlff_assemble_sgdml, the energy border of
+ * mlff_set_energy_constraints included).  The lower triangle is copied, sign and shift applied,
+ * into an N x N scratch matrix, factored by a two-level blocked Cholesky (64-wide steps inside
+ * panels of MLFF_POTRF_OUTER columns, read once, default 256; one trailing update per panel on
+ * the matrix cores) and solved forward and backward with 64 unknowns per step; K, the operator
+ * and a preconditioner of the context stay as they are.  The reference calls this with
+ * sigma_K = -1, shift = 1e-10 whatever task['lam'] says (analytic.py:136).  One rank
+ * (MLFF_ERR_ARG otherwise); MLFF_ERR_STATE without a dense matrix (a matrix-free operator
+ * alone); MLFF_ERR_NOMEM when the scratch does not fit; MLFF_ERR_LINALG (-> LinAlgError) on a
+ * non-positive pivot -- the reference then falls back to LU (analytic.py:154-167), this does
+ * not.  seconds_out (3, optional): device seconds of the copy, the factorisation and the two
+ * triangular solves (stream events). */
+int mlff_dense_cho_solve(mlff_ctx *ctx, double sigma_K, double shift, const double *b,
+                         double *x_out, double *seconds_out);
+/* Test hook (no reference counterpart): the lower Cholesky factor L_out (n x n, row-major,
+ * upper triangle zero) of the lower triangle of the host matrix A, variant 0 by the one-level
+ * factorisation of the Woodbury builds, 1 by the two-level one of mlff_dense_cho_solve;
+ * seconds_out (optional): device seconds of the factorisation.  MLFF_ERR_LINALG on a
+ * non-positive pivot. */
+int mlff_test_potrf(mlff_ctx *ctx, const double *A, int64_t n, int variant, double *L_out,
+                    double *seconds_out);
 /* Gram matrix G = W W^T (k x k, row-major) of a host k x ncols panel W (row-major) as the
  * Woodbury build forms L^T L (iterative_cholesky.py:141-142, `kernel = lam I + L^T L`):
  * mode 0 the fp64 matrix-core SYRK, 1 fp64 64-column chunks summed in double-double (the

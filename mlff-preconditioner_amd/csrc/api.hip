@@ -1524,6 +1524,31 @@ int mlff_test_gemm(mlff_ctx *ctx, int ta, int tb, int64_t M, int64_t N, int64_t 
   MLFF_API_END(ctx)
 }
 
+int mlff_test_potrf(mlff_ctx *ctx, const double *A, int64_t n, int variant, double *L_out,
+                    double *seconds_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  if (A == nullptr || L_out == nullptr || n < 1 || variant < 0 || variant > 1)
+    return set_error(ctx, MLFF_ERR_ARG, "test_potrf: bad arguments");
+  return test_potrf(ctx, A, n, variant, L_out, seconds_out);
+  MLFF_API_END(ctx)
+}
+
+int mlff_dense_cho_solve(mlff_ctx *ctx, double sigma_K, double shift, const double *b,
+                         double *x_out, double *seconds_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  if (b == nullptr || x_out == nullptr) return set_error(ctx, MLFF_ERR_ARG, "null pointer");
+  if (ctx->world > 1)
+    return set_error(ctx, MLFF_ERR_ARG, "dense_cho_solve: the closed-form solve runs on one rank");
+  if (!ctx->has_matrix)
+    return set_error(ctx, MLFF_ERR_STATE,
+                     "dense_cho_solve: no dense kernel matrix (mlff_set_matrix_host / "
+                     "mlff_assemble_sgdml); a matrix-free operator alone cannot be factored");
+  return dense_cho_solve(ctx, sigma_K, shift, b, x_out, seconds_out);
+  MLFF_API_END(ctx)
+}
+
 int mlff_test_gram(mlff_ctx *ctx, const double *W, int64_t k, int64_t ncols, int mode,
                    double *G_out) {
   MLFF_API_BEGIN

@@ -718,6 +718,29 @@ int trsm_lower_wide(mlff_ctx *ctx, const double *L, int64_t k, double *W, int64_
                     int64_t ldw);
 void launch_add_diag(double *A, int64_t k, double v, hipStream_t s);
 void launch_zero_upper(double *A, int64_t k, hipStream_t s);
+// potrf_lower's steps on their own: the jb x jb diagonal block at (j0, j0) in one wave (err set
+// on a non-positive pivot), the panel solve of the rows below it, and launch_gemm restricted
+// to the tiles that touch the lower triangle of C
+void launch_potrf_diag_wave(double *A, int64_t lda, int64_t j0, int jb, int *err, hipStream_t s);
+void launch_trsm_panel(double *A, int64_t lda, int64_t k, int64_t j0, int jb, hipStream_t s);
+void launch_gemm_tri(bool ta, bool tb, int64_t M, int64_t Nc, int64_t Kd, double alpha,
+                     const double *A, int64_t lda, const double *B, int64_t ldb, double beta,
+                     double *C, int64_t ldc, hipStream_t s);
+
+// ---- closed-form dense solve (kernels_chol.hip) -------------------------------
+// potrf_lower in a two-level order: its 64-wide steps inside a panel of MLFF_POTRF_OUTER
+// columns (default 256; 64: potrf_lower's order), one trailing update per panel
+int potrf_lower_blocked(mlff_ctx *ctx, double *A, int64_t n, bool *ok_out = nullptr);
+// x <- L^-1 x and x <- L^-T x for a row-major lower factor (ld = n), one right-hand side
+int trsv_lower_fwd(mlff_ctx *ctx, const double *L, int64_t n, double *x);
+int trsv_lower_bwd(mlff_ctx *ctx, const double *L, int64_t n, double *x);
+// (sigma_K K + shift I) x = b with the context's dense rows (one rank), host vectors;
+// seconds_out (3, optional): copy / factor / solves
+int dense_cho_solve(mlff_ctx *ctx, double sigma_K, double shift, const double *b_host,
+                    double *x_host, double *seconds_out);
+// test hook: lower factor of a host matrix, variant 0 potrf_lower / 1 potrf_lower_blocked
+int test_potrf(mlff_ctx *ctx, const double *A_host, int64_t n, int variant, double *L_host,
+               double *seconds_out);
 // column sums of squares: out[c] = sum_j W[j, c]^2
 void launch_colsumsq(const double *W, int64_t k, int64_t ncols, int64_t ldw, double *out,
                      hipStream_t s);

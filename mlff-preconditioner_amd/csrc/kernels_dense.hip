@@ -536,6 +536,25 @@ int potrf_lower(mlff_ctx *ctx, double *A, int64_t k, bool *ok_out) {
   return MLFF_OK;
 }
 
+// potrf_lower's three steps for the two-level order of kernels_chol.hip (potrf_lower_blocked):
+// the same kernels, launched on other ranges
+void launch_potrf_diag_wave(double *A, int64_t lda, int64_t j0, int jb, int *err, hipStream_t s) {
+  hipLaunchKernelGGL(k_potrf_diag_wave, dim3(1), dim3(64), 0, s, A, lda, j0, jb, err);
+}
+
+void launch_trsm_panel(double *A, int64_t lda, int64_t k, int64_t j0, int jb, hipStream_t s) {
+  const int64_t rest = k - j0 - jb;
+  if (rest <= 0) return;
+  hipLaunchKernelGGL(k_trsm_panel, dim3((unsigned)((rest + 63) / 64)), dim3(64), 0, s, A, lda, k,
+                     j0, jb);
+}
+
+void launch_gemm_tri(bool ta, bool tb, int64_t M, int64_t Nc, int64_t Kd, double alpha,
+                     const double *A, int64_t lda, const double *B, int64_t ldb, double beta,
+                     double *C, int64_t ldc, hipStream_t s) {
+  gemm_launch(ta, tb, M, Nc, Kd, alpha, A, lda, B, ldb, beta, C, ldc, 1, 0, s, 1);
+}
+
 // ---------------------------------------------------------------------------
 // W[i0:i0+ib, :] <- L_ii^-1 W[i0:i0+ib, :], one thread per column.
 __global__ __launch_bounds__(256) void k_trsm_diag_wide(const double *__restrict__ Lm, int64_t k,

@@ -1,21 +1,26 @@
 """Training entry point and the reference's on-disk model format.
 
-`train(task, ...)` is GDMLTrain.train for solver 'cg' (src/sGDML/sgdml/train.py:707-970)
-with the solve on the MI355X: label vector y = F / std(F) (:837-845), lambda = 1e-10
-(:866), `Iterative.solve` (the drop-in, :868-890), `create_model` (:597-702),
-`model.update(info)` (:938-939) and the integration constant `_recov_int_const`
-(:972-1119) from the training-set energies predicted on the GPU
-(`mlff_sgdml_energies`, the E part of GDMLPredict, predict.py:172-220).  The returned
-dict has the reference model's keys and meanings, so `store_model` (train_models.py
-:127-154) writes the same `.npz` that the reference's analysis scripts read.
+`train(task, ...)` is GDMLTrain.train for the solvers 'cg' and 'analytic'
+(src/sGDML/sgdml/train.py:707-970) with the solve on the MI355X: label vector y = F / std(F),
+with use_E_cstr [F; -E + mean(E)] / std (:837-845); for 'cg' lambda = 1e-10 (:866),
+`Iterative.solve` (the drop-in, :868-890) and `model.update(info)` (:938-939); for 'analytic'
+`Analytic.solve` (:851-857: dense assembly, Cholesky factorisation and triangular solves on
+the device, energy constraints included); `create_model` (:597-702) and the integration
+constant: the mean training energy with use_E_cstr, otherwise `_recov_int_const` (:972-1119)
+from the training-set energies predicted on the GPU (`mlff_sgdml_energies`, the E part of
+GDMLPredict, predict.py:172-220).  The returned dict has the reference model's keys and
+meanings, so `store_model` (train_models.py:127-154) writes the same `.npz` that the
+reference's analysis scripts read.
 
 `test_errors(model, R, F, E)` is the reference's test step (cli.py:855-865, 1217-1245): the
 model's energies and forces at held-out geometries, predicted on the GPU by
 `sgdml_amd.predict.GDMLPredict`, and their mean absolute / root mean square errors, which it
 can write into the model's `f_err` / `e_err` / `n_test` fields.
 
-Not covered (out of the solve path): symmetry compression (`use_cprsn`),
-energy constraints (`use_E_cstr`), periodic lattices, the 'analytic' solver.
+Not covered: symmetry compression (`use_cprsn`), periodic lattices, the 'cg_cholesky' solver
+name, the closed-form solver's LU / least-squares fallbacks and more than one device for it,
+and prediction with energy-constrained models (`alphas_E`; GDMLPredict refuses them).  Energy
+constraints (`use_E_cstr`) train with 'analytic' only, as in the reference.
 """
 from __future__ import annotations
 
@@ -193,15 +198,18 @@ class _ModelFactory:
 def train(task, cprsn_callback=None, save_progr_callback=None, callback=None,
           break_percentage=0.1, n_columns=None, str_preconditioner="", flag_eigvals=False,
           device=None, devices=None, gdml_train=None):
-    """GDMLTrain.train (train.py:707-970) for solver 'cg' on the MI355X."""
+    """GDMLTrain.train (train.py:707-970) for the solvers 'cg' and 'analytic' on the MI355X."""
     from .solvers import Iterative
 
     task = dict(task)
     solver_name = task["solver_name"]
-    if solver_name != "cg":
-        raise NotImplementedError(f"solver '{solver_name}': only the iterative 'cg' path runs here")
+    if solver_name not in ("cg", "analytic"):
+        raise NotImplementedError(f"solver '{solver_name}': only the iterative 'cg' and the "
+                                  "closed-form 'analytic' paths run here")
     if task.get("use_cprsn", False) or "lattice" in task:
         raise NotImplementedError("symmetry compression / periodic lattices are not supported")
+    if solver_name == "analytic":
+        return _train_analytic(task, callback, device, devices)
     if task.get("use_E", False) and task.get("use_E_cstr", False):
         # as the reference's train -> Iterative.solve (see Iterative.solve)
         raise ValueError("use_E_cstr: the reference's iterative solve cannot run with energy "
@@ -241,17 +249,69 @@ def train(task, cprsn_callback=None, save_progr_callback=None, callback=None,
     return model
 
 
+def label_vector(task) -> tuple[np.ndarray, float, float | None]:
+    """The label vector of GDMLTrain.train (train.py:836-845): (y / std(y), std(y), mean
+    training energy or None); y = F, and [F; -E + mean(E)] with use_E and use_E_cstr."""
+    E_train_mean = None
+    y = np.asarray(task["F_train"]).ravel().copy()
+    if task["use_E"] and task["use_E_cstr"]:
+        E_train = np.asarray(task["E_train"]).ravel().copy()
+        E_train_mean = np.mean(E_train)
+        y = np.hstack((y, -E_train + E_train_mean))
+    y_std = np.std(y)
+    y /= y_std
+    return y, y_std, E_train_mean
+
+
+def _train_analytic(task, callback, device, devices):
+    """The solver == 'analytic' branch of GDMLTrain.train (train.py:851-857, 929-970):
+    task['lam'] stays as given (only 'cg' forces 1e-10), no solver_resid / solver_iters /
+    inducing_pts_idxs and no info update."""
+    from .solvers import Analytic
+
+    if devices is not None and len(devices) > 1:
+        raise NotImplementedError("the closed-form solve runs on one device")
+    if devices is not None and len(devices) == 1 and device is None:
+        device = int(devices[0])
+    n_train = task["R_train"].shape[0]
+    tpl = tril_perms_lin(np.atleast_2d(np.asarray(task["perms"])))
+    R_desc, R_d_desc = host_descriptors(np.asarray(task["R_train"], dtype=np.float64))
+    y, y_std, E_train_mean = label_vector(task)
+    with Analytic(None, None, callback=callback, device=device) as an:
+        alphas = an.solve(task, R_desc, R_d_desc, tpl, y)
+        alphas_E = None
+        alphas_F = alphas
+        if task["use_E_cstr"]:                              # train.py:929-933
+            alphas_E = alphas[-n_train:]
+            alphas_F = alphas[:-n_train]
+        model = create_model(task, "analytic", R_desc, R_d_desc, tpl, y_std, alphas_F,
+                             alphas_E=alphas_E, norm_y_train=np.linalg.norm(y))
+        if model["use_E"]:                                  # train.py:956-966
+            if E_train_mean is None:
+                _, E = an.solver.sgdml_energies(alphas)
+                c = recov_int_const(E * y_std, task["E_train"])
+            else:
+                c = E_train_mean
+            if c is None:
+                model["use_E"] = False
+            else:
+                model["c"] = c
+    return model
+
+
 def train_model(task, name_dataset: str, n_datapoints: int, preconditioner: str,
-                hardware: str = "mi355x", devices=None) -> dict:
+                hardware: str = "mi355x", devices=None, solver: str = "cg") -> dict:
     """The solve part of src/train_models.py:train_model (:68-124) for a task the caller
     built (dataset download and GDMLTrain.create_task stay with the reference):
-    rule-of-thumb preconditioner size (:95-97), train, and the bookkeeping keys
-    store_model and the analysis scripts read (:104-113)."""
+    rule-of-thumb preconditioner size (:95-97), train with `solver` ('cg' or 'analytic', the
+    loop of :161-167), and the bookkeeping keys store_model and the analysis scripts read
+    (:104-113)."""
     import timeit
 
     from .rule_of_thumb import get_params, rule_of_thumb
 
     task = dict(task)
+    task["solver_name"] = solver
     task["truncated_cholesky"] = 1500
     task["str_preconditioner"] = preconditioner
     n = task["F_train"].size

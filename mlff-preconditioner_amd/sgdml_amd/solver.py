@@ -253,6 +253,35 @@ class KernelSolver:
         self._call("mlff_spectrum", int(bool(preconditioned)), nat.dptr(out))
         return out
 
+    def dense_cho_solve(self, b: np.ndarray, sigma_K: float = -1.0, shift: float = 1e-10,
+                        want_seconds: bool = False):
+        """x = (sigma_K K + shift I)^-1 b by a dense Cholesky factorisation of the context's
+        matrix (set_matrix / assemble_sgdml) on the device: the reference's closed-form solve
+        (analytic.py:129-153; its call is the default sigma_K = -1, shift = 1e-10).  K and the
+        operator stay usable.  One rank; LinAlgError when a pivot is not positive (no LU
+        fallback).  want_seconds: also the device seconds (copy, factor, solves)."""
+        b = np.ascontiguousarray(b, dtype=np.float64)
+        if b.shape != (self.n,):
+            raise ValueError("b must have N entries")
+        x = np.empty(self.n)
+        sec = np.zeros(3)
+        self._call("mlff_dense_cho_solve", float(sigma_K), float(shift), nat.dptr(b), nat.dptr(x),
+                   nat.dptr(sec))
+        return (x, sec) if want_seconds else x
+
+    def test_potrf(self, A: np.ndarray, variant: int = 1, want_seconds: bool = False):
+        """Lower Cholesky factor of A's lower triangle on the device: variant 0 the one-level
+        factorisation of the preconditioner builds, 1 the two-level one of dense_cho_solve
+        (test hook, mlff_test_potrf)."""
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        if A.ndim != 2 or A.shape[0] != A.shape[1]:
+            raise ValueError("A must be square")
+        L = np.empty_like(A)
+        sec = ctypes.c_double()
+        self._call("mlff_test_potrf", nat.dptr(A), A.shape[0], int(variant), nat.dptr(L),
+                   ctypes.byref(sec))
+        return (L, sec.value) if want_seconds else L
+
     def diag(self) -> np.ndarray:
         d = np.empty(self.nrows)
         self._call("mlff_get_diag", nat.dptr(d))
