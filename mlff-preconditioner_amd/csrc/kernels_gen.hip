@@ -4,6 +4,8 @@
 //  - sGDML inverse-distance descriptors (utils/desc.py:80-234)
 // Column positions use the padded rank-block layout of the context:
 //   pos(g) = (g / rows_per) * blk + g % rows_per.
+#include <set>
+
 #include "common.h"
 #include "sgdml_col.h"
 
@@ -164,7 +166,8 @@ void launch_gather_mm(const double *W, int64_t ldw, const int64_t *idx, int64_t 
 // The reference assembles the lower block triangle and mirrors it
 // (train.py:172-210, exploit_sym): block (i, j) = Blk(r=i, s=j) for j < i and
 // Blk(r=j, s=i)^T for j >= i (a diagonal block is stored transposed, which only
-// matters for permutation sets that are not a group).  A record (i_loc, j)
+// matters for permutation sets that are not a group; for a set closed under inversion its
+// upper triangle is written as the mirror of its lower one, k_sgdml_block).  A record (i_loc, j)
 // therefore holds the quantities of the pair (r, s) = (i, j) if j < i else (j, i).
 //
 // one workgroup per (j, i_loc, p): norm, m_p, w_p, u[p, :] (row point r), v[p, :] (col point s)
@@ -290,7 +293,7 @@ __global__ __launch_bounds__(256) void k_sgdml_block(double *__restrict__ K, int
                                                      const int32_t *__restrict__ piinv,
                                                      int n_perms,
                                                      const double *__restrict__ uv, int jdiag,
-                                                     double *__restrict__ diag_out) {
+                                                     double *__restrict__ diag_out, int symdiag) {
   const int beta = blockIdx.x;
   const int64_t iloc = blockIdx.y;
   const int64_t i = i0 + iloc;
@@ -311,82 +314,75 @@ __global__ __launch_bounds__(256) void k_sgdml_block(double *__restrict__ K, int
   __shared__ double red[4][9];
   const double *rddr = Rdd + rp * D * 3;
   const double *rdds = Rdd + sp * D * 3;
-  for (int p = 0; p < n_perms; ++p) {
-    const int32_t *pp = pi + (int64_t)p * n;
-    // mode A: row atom beta; mode B: the row atom of r mapped onto beta
-    const int x = modeA ? beta : piinv[(int64_t)p * n + beta];
-    sgdml_gdiag(rddr, rdds, pp, n, x, red, gdiag + p * 9);
-  }
   const int64_t rec_stride = 6 * n + 2;
-  for (int t = threadIdx.x; t < n3; t += 256) {
-    const int alpha = t / 3, cc = t % 3;
-    double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0;
+  // The entry (row (beta, c), column (alpha, cc)) is the element Blk[(xa, xc), (ya, yc)] of the
+  // block of the pair (r, s): ((beta, c), (alpha, cc)) in orientation A, ((alpha, cc), (beta, c))
+  // in orientation B (the transposed block).  Off the block diagonal the whole block has one
+  // orientation, and the mirrored block (j, i) the other: the same elements, the same
+  // arithmetic, so K is symmetric to the bit.  A diagonal block (r = s = i) is stored transposed
+  // by the reference (orientation B throughout).  For a permutation set closed under inversion
+  // that block is symmetric, but from more than one permutation only to rounding; with symdiag
+  // its lower triangle and diagonal take orientation B (the reference's entries) and the upper
+  // triangle orientation A -- the element its mirror entry holds -- in a pass of its own, since
+  // the atom-diagonal term G below is tabulated for one row atom of r per pass.  (A set that is
+  // not closed has an unsymmetric diagonal block in the reference too: kept as it is.)
+  const bool dblk = symdiag && j == i && diag_out == nullptr;
+  for (int pass = dblk ? 0 : 1; pass < 2; ++pass) {
+    const bool oA = dblk ? pass == 0 : modeA;
+    if (dblk && pass == 1) __syncthreads();  // pass 0 has read gdiag
     for (int p = 0; p < n_perms; ++p) {
-      const double *rec = uv + ((iloc * M + jslot) * n_perms + p) * rec_stride;
-      const double m5 = 5.0 * rec[6 * n];
-      const double w = rec[6 * n + 1];
       const int32_t *pp = pi + (int64_t)p * n;
-      const int32_t *pq = piinv + (int64_t)p * n;
-      double g0, g1, g2, t0, t1, t2;
-      if (modeA) {
-        // K[(beta,c),(alpha,cc)] = m5 u[beta,c] v[alpha,cc] - w G(beta,c; alpha,cc)
-        const double vv = rec[n3 + t];
-        t0 = m5 * rec[3 * beta] * vv;
-        t1 = m5 * rec[3 * beta + 1] * vv;
-        t2 = m5 * rec[3 * beta + 2] * vv;
-        const int ai = pq[alpha];
-        if (ai == beta) {
-          g0 = gdiag[p * 9 + 0 * 3 + cc];
-          g1 = gdiag[p * 9 + 1 * 3 + cc];
-          g2 = gdiag[p * 9 + 2 * 3 + cc];
-        } else {
-          const int64_t d = pair_idx(beta, ai);
-          const double sd = pair_sign(beta, ai);
-          const int pb = pp[beta];
-          const int64_t e = pair_idx(alpha, pb);
-          const double jv = pair_sign(alpha, pb) * rdds[e * 3 + cc];
-          g0 = sd * rddr[d * 3 + 0] * jv;
-          g1 = sd * rddr[d * 3 + 1] * jv;
-          g2 = sd * rddr[d * 3 + 2] * jv;
+      // orientation A: row atom beta; B: the row atom of r mapped onto beta
+      const int x = oA ? beta : piinv[(int64_t)p * n + beta];
+      sgdml_gdiag(rddr, rdds, pp, n, x, red, gdiag + p * 9);
+    }
+    for (int t = threadIdx.x; t < n3; t += 256) {
+      const int alpha = t / 3, cc = t % 3;
+      // r-side (xa, xc) and s-side (ya, yc) indices of the element; the component on the side
+      // of the three rows runs over c below
+      const int xa = oA ? beta : alpha, ya = oA ? alpha : beta;
+      double acc[3] = {0.0, 0.0, 0.0};
+      for (int p = 0; p < n_perms; ++p) {
+        const double *rec = uv + ((iloc * M + jslot) * n_perms + p) * rec_stride;
+        const double m5 = 5.0 * rec[6 * n];
+        const double w = rec[6 * n + 1];
+        const int32_t *pp = pi + (int64_t)p * n;
+        const int32_t *pq = piinv + (int64_t)p * n;
+        // Blk[(xa,xc),(ya,yc)] = m5 u[xa,xc] v[ya,yc] - w G(xa,xc; ya,yc),
+        // G = J_r^T J_s[P_p]: the atom-diagonal table where pi^-1(ya) = xa, else one product
+        const int ai = pq[ya];
+        const bool gd = ai == xa;
+        int64_t d = 0, e = 0;
+        double sd = 0.0, se = 0.0;
+        if (!gd) {
+          d = pair_idx(xa, ai);
+          sd = pair_sign(xa, ai);
+          const int pb = pp[xa];
+          e = pair_idx(ya, pb);
+          se = pair_sign(ya, pb);
         }
-      } else {
-        // K[(beta,c),(alpha,cc)] = Blk_{r=j,s=i}[(alpha,cc),(beta,c)]
-        //   = m5 u[alpha,cc] v[beta,c] - w G(alpha,cc; beta,c)
-        const double uu = m5 * rec[t];
-        t0 = uu * rec[n3 + 3 * beta];
-        t1 = uu * rec[n3 + 3 * beta + 1];
-        t2 = uu * rec[n3 + 3 * beta + 2];
-        const int xs = pq[beta];  // row atom of r whose image is beta
-        if (alpha == xs) {
-          g0 = gdiag[p * 9 + cc * 3 + 0];
-          g1 = gdiag[p * 9 + cc * 3 + 1];
-          g2 = gdiag[p * 9 + cc * 3 + 2];
-        } else {
-          const int64_t d = pair_idx(alpha, xs);
-          const double sd = pair_sign(alpha, xs);
-          const double dv = sd * rddr[d * 3 + cc];
-          const int pa = pp[alpha];
-          const int64_t e = pair_idx(beta, pa);
-          const double se = pair_sign(beta, pa);
-          g0 = dv * (se * rdds[e * 3 + 0]);
-          g1 = dv * (se * rdds[e * 3 + 1]);
-          g2 = dv * (se * rdds[e * 3 + 2]);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          const int xc = oA ? c : cc, yc = oA ? cc : c;
+          const double uu = m5 * rec[3 * xa + xc];
+          const double vv = rec[n3 + 3 * ya + yc];
+          const double g = gd ? gdiag[p * 9 + xc * 3 + yc]
+                              : (sd * rddr[d * 3 + xc]) * (se * rdds[e * 3 + yc]);
+          acc[c] += uu * vv - w * g;
         }
       }
-      acc0 += t0 - w * g0;
-      acc1 += t1 - w * g1;
-      acc2 += t2 - w * g2;
-    }
-    const int64_t gcol = j * n3 + t;
-    const int64_t pos = col_pos(gcol, rows_per, blk);
-    const double accs[3] = {acc0, acc1, acc2};
-    for (int c = 0; c < 3; ++c) {
-      const int64_t g = grow0 + c;
-      if (g < row0 || g >= row0 + nrows) continue;
-      if (diag_out != nullptr) {
-        if (gcol == g) diag_out[g - row0] = accs[c];
-      } else {
-        K[(g - row0) * ld + pos] = accs[c];
+      const int64_t gcol = j * n3 + t;
+      const int64_t pos = col_pos(gcol, rows_per, blk);
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        const int64_t g = grow0 + c;
+        if (g < row0 || g >= row0 + nrows) continue;
+        if (dblk && (gcol > g) != oA) continue;  // the other pass's triangle
+        if (diag_out != nullptr) {
+          if (gcol == g) diag_out[g - row0] = acc[c];
+        } else {
+          K[(g - row0) * ld + pos] = acc[c];
+        }
       }
     }
   }
@@ -478,6 +474,18 @@ int desc_perm_tables(mlff_ctx *ctx, const int32_t *perms, int n, int n_perms,
   return MLFF_OK;
 }
 
+// every permutation's inverse is in the set (true of a group): K's diagonal blocks are symmetric
+static bool perms_closed_under_inversion(const int32_t *perms, const std::vector<int32_t> &piinv,
+                                         int n, int n_perms) {
+  std::set<std::vector<int32_t>> rows;
+  for (int p = 0; p < n_perms; ++p) rows.emplace(perms + (size_t)p * n, perms + (size_t)(p + 1) * n);
+  for (int p = 0; p < n_perms; ++p)
+    if (rows.count(std::vector<int32_t>(piinv.begin() + (size_t)p * n,
+                                        piinv.begin() + (size_t)(p + 1) * n)) == 0)
+      return false;
+  return true;
+}
+
 int assemble_sgdml(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc, int64_t M,
                    int n_atoms, const int32_t *perms, int n_perms, double sig) {
   const int n = n_atoms;
@@ -521,7 +529,7 @@ int assemble_sgdml(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc, 
     hipLaunchKernelGGL(k_sgdml_block, dim3((unsigned)n, (unsigned)mi, (unsigned)M), dim3(256),
                        sizeof(double) * 9 * n_perms, s, ctx->K, ctx->ld, ctx->row0, ctx->nrows,
                        ctx->rows_per, ctx->blk, dRdd, M, n, D, i0, dpi, dpiinv, n_perms, uv, 0,
-                       (double *)nullptr);
+                       (double *)nullptr, (int)perms_closed_under_inversion(perms, piinv, n, n_perms));
   }
   if (E) {  // one rank: rows and columns are global indices
     const double rec_bytes = 8.0 * (double)M * (double)M * n_perms * (double)rec;
@@ -569,7 +577,7 @@ int sgdml_diag(mlff_ctx *ctx, const double *dRd, const double *dRdd, int64_t M, 
   hipLaunchKernelGGL(k_sgdml_block, dim3((unsigned)n, (unsigned)mi, 1), dim3(256),
                      sizeof(double) * 9 * n_perms, s, (double *)nullptr, ctx->ld, ctx->row0,
                      nrows, ctx->rows_per, ctx->blk, dRdd, (int64_t)1, n, D, i0, dpi, dpiinv,
-                     n_perms, uv, 1, diag_out);
+                     n_perms, uv, 1, diag_out, 0);
   MLFF_HIP(ctx, hipGetLastError());
   return MLFF_OK;
 }

@@ -7,11 +7,24 @@ from __future__ import annotations
 import numpy as np
 
 
-def descriptors(R):
+def _sqrt5(dtype):
+    return np.sqrt(dtype(5))
+
+
+def _typed(dtype, sig, *arrays):
+    """sig and the arrays in `dtype`.  float64: sig as given and float64 arrays untouched, so
+    the default evaluation keeps its operations and their order; np.longdouble: every operand
+    widened before the first product (tests/sgdml_shapes.py: the high-precision reference)."""
+    if dtype is not np.float64:
+        sig = dtype(sig)
+    return (sig,) + tuple(np.asarray(a, dtype=dtype) for a in arrays)
+
+
+def descriptors(R, dtype=np.float64):
     """Desc.from_R without cutoff / PBC (desc.py:80-234, 292-358).
     R: M x n x 3  ->  R_desc (M x D) = 1/r_ab, R_d_desc (M x D x 3) = (r_a - r_b)/r_ab^3,
     pairs (a, b) in np.tril_indices(n, -1) order."""
-    R = np.asarray(R, dtype=np.float64)
+    R = np.asarray(R, dtype=dtype)
     M, n, _ = R.shape
     a, b = np.tril_indices(n, k=-1)
     pdiff = R[:, a, :] - R[:, b, :]
@@ -44,26 +57,27 @@ def d_desc_from_comp(R_d_desc, n):
     """desc.py:444-462: compact (D x 3) Jacobian -> full (D x 3n)."""
     D = R_d_desc.shape[0]
     i, j = np.tril_indices(n, k=-1)
-    out = np.zeros((D, n, 3))
+    out = np.zeros((D, n, 3), dtype=R_d_desc.dtype)
     out[np.arange(D), j, :] = R_d_desc
     out[np.arange(D), i, :] = -R_d_desc
     return out.reshape(D, 3 * n)
 
 
-def assemble_kernel(R_desc, R_d_desc, tril_perms_lin_, sig, use_E_cstr=False):
+def assemble_kernel(R_desc, R_d_desc, tril_perms_lin_, sig, use_E_cstr=False, dtype=np.float64):
     """GDMLTrain._assemble_kernel_mat with col_idxs = all (train.py:81-236, 1121-1308).
     use_E_cstr: M energy rows / columns appended (train.py:212-236, 1205-1208), filled by
     column worker j for every row point i in increasing j (the order a one-process Pool
     runs the workers in, so for a non-group permutation set the E-E entry (a, b) holds
     the value of worker max(a, b))."""
+    sig, R_desc, R_d_desc = _typed(dtype, sig, R_desc, R_d_desc)
     M, D = R_desc.shape
     n = int((1 + np.sqrt(8 * D + 1)) / 2)
     dim_i = 3 * n
     n_perms = int(len(tril_perms_lin_) / D)
     nE = M if use_E_cstr else 0
-    K = np.empty((M * dim_i + nE, M * dim_i + nE))
+    K = np.empty((M * dim_i + nE, M * dim_i + nE), dtype=dtype)
     mat52_base_div = 3 * sig ** 4
-    sqrt5 = np.sqrt(5.0)
+    sqrt5 = _sqrt5(dtype)
     sig_pow2 = sig ** 2
     J = [d_desc_from_comp(R_d_desc[m], n) for m in range(M)]
     for j in range(M):
@@ -95,7 +109,7 @@ def assemble_kernel(R_desc, R_d_desc, tril_perms_lin_, sig, use_E_cstr=False):
     return K
 
 
-def kernel_matvec_matrix_free(R_desc, R_d_desc, perms, sig, x, use_E_cstr=False):
+def kernel_matvec_matrix_free(R_desc, R_d_desc, perms, sig, x, use_E_cstr=False, dtype=np.float64):
     """K x without forming K, as the reference's CG operator evaluates it: the
     force prediction of GDMLPredict with alphas = x (predict.py:72-234, set_alphas
     :400-445, Desc.d_desc_dot_vec / vec_dot_d_desc desc.py:464-508) for every
@@ -111,21 +125,21 @@ def kernel_matvec_matrix_free(R_desc, R_d_desc, perms, sig, x, use_E_cstr=False)
         F_i     += sum_jp x_E[j] w diff
         out_E_i  = -(sum_jp a_ijp w + sum_jp K_ee x_E[j]),
         K_ee     = (1 + norm/sig (1 + norm/(3 sig))) exp(-norm/sig)."""
-    R_desc = np.asarray(R_desc, dtype=np.float64)
+    sig, R_desc, R_d_desc = _typed(dtype, sig, R_desc, R_d_desc)
     M, D = R_desc.shape
     n = int((1 + np.sqrt(8 * D + 1)) / 2)
     perms = np.atleast_2d(perms)
     P = np.array([desc_perm(p) for p in perms])  # n_perms x D descriptor maps
     s_at, t_at = np.tril_indices(n, k=-1)          # pair d = (s, t), s > t
-    x = np.asarray(x, dtype=np.float64)
+    x = np.asarray(x, dtype=dtype)
     xE = x[3 * n * M:] if use_E_cstr else None
     X = x[:3 * n * M].reshape(M, n, 3)
-    outE = np.empty(M)
+    outE = np.empty(M, dtype=dtype)
     z = np.einsum("mdc,mdc->md", R_d_desc, X[:, t_at, :] - X[:, s_at, :])
     Rt = R_desc[:, P]                               # M x n_perms x D: Rd_j[P_p d]
     Zt = z[:, P]
-    sqrt5 = np.sqrt(5.0)
-    y = np.empty((M, n, 3))
+    sqrt5 = _sqrt5(dtype)
+    y = np.empty((M, n, 3), dtype=dtype)
     for i in range(M):
         diff = R_desc[i][None, None, :] - Rt        # M x n_perms x D
         norm = sqrt5 * np.linalg.norm(diff, axis=2)
@@ -139,14 +153,14 @@ def kernel_matvec_matrix_free(R_desc, R_d_desc, perms, sig, x, use_E_cstr=False)
             outE[i] = -(np.sum(a * w) + np.sum(kee * xE[:, None]))
         # y_i = J_i^T F: atom t gets +Rdd F, atom s gets -Rdd F
         contrib = R_d_desc[i] * F[:, None]
-        yi = np.zeros((n, 3))
+        yi = np.zeros((n, 3), dtype=dtype)
         np.add.at(yi, t_at, contrib)
         np.add.at(yi, s_at, -contrib)
         y[i] = yi
     return np.concatenate([y.reshape(-1), outE]) if use_E_cstr else y.reshape(-1)
 
 
-def kernel_column_matrix_free(R_desc, R_d_desc, perms, sig, g):
+def kernel_column_matrix_free(R_desc, R_d_desc, perms, sig, g, dtype=np.float64):
     """K e_g of kernel_matvec_matrix_free (the reference's get_col through K_op,
     iterative_cholesky.py:152-156 with predict.py:72-234) from the one training point it touches:
     e_g (g = j 3n + 3a + c) makes z_j = J_j e_(a,c) the only non-zero z, so
@@ -155,20 +169,20 @@ def kernel_column_matrix_free(R_desc, R_d_desc, perms, sig, g):
     the zero terms of the other training points left out, so the column equals K_op e_g to the
     rounding of its sums (<= 3e-16 of its largest entry,
     tests/test_oracle_golden.py::test_column_restatement_matches_operator)."""
-    R_desc = np.asarray(R_desc, dtype=np.float64)
+    sig, R_desc, R_d_desc = _typed(dtype, sig, R_desc, R_d_desc)
     M, D = R_desc.shape
     n = int((1 + np.sqrt(8 * D + 1)) / 2)
     perms = np.atleast_2d(perms)
     P = np.array([desc_perm(p) for p in perms])
     s_at, t_at = np.tril_indices(n, k=-1)
     j, a, c = g // (3 * n), (g % (3 * n)) // 3, g % 3
-    X = np.zeros((n, 3))
+    X = np.zeros((n, 3), dtype=dtype)
     X[a, c] = 1.0
     z = np.einsum("dc,dc->d", R_d_desc[j], X[t_at, :] - X[s_at, :])   # J_j e_(a,c)
     Rt = R_desc[j][P][None]                         # 1 x n_perms x D
     Zt = z[P][None]
-    sqrt5 = np.sqrt(5.0)
-    y = np.empty((M, n, 3))
+    sqrt5 = _sqrt5(dtype)
+    y = np.empty((M, n, 3), dtype=dtype)
     for i in range(M):
         diff = R_desc[i][None, None, :] - Rt
         norm = sqrt5 * np.linalg.norm(diff, axis=2)
@@ -177,29 +191,29 @@ def kernel_column_matrix_free(R_desc, R_d_desc, perms, sig, g):
         aa = np.einsum("jpd,jpd->jp", diff, Zt)
         F = np.einsum("jp,jpd->d", 5.0 * m * aa, diff) - np.einsum("jp,jpd->d", w, Zt)
         contrib = R_d_desc[i] * F[:, None]
-        yi = np.zeros((n, 3))
+        yi = np.zeros((n, 3), dtype=dtype)
         np.add.at(yi, t_at, contrib)
         np.add.at(yi, s_at, -contrib)
         y[i] = yi
     return y.reshape(-1)
 
 
-def pair_records(R_desc, R_d_desc, perms, sig):
+def pair_records(R_desc, R_d_desc, perms, sig, dtype=np.float64):
     """The x-independent per-(i, j, p) quantities of the operator above, as the GPU keeps
     them (kernels_gen.hip k_sgdml_uv, mirror = 0): u = J_i^T diff (query point side),
     v = J_j^T P_p^T diff (training point side, 3n each), 5 m and w.
     Returns U, V (M x M x n_perms x 3n), m5, w (M x M x n_perms)."""
-    R_desc = np.asarray(R_desc, dtype=np.float64)
+    sig, R_desc, R_d_desc = _typed(dtype, sig, R_desc, R_d_desc)
     M, D = R_desc.shape
     n = int((1 + np.sqrt(8 * D + 1)) / 2)
     P = np.array([desc_perm(p) for p in np.atleast_2d(perms)])
     npm = P.shape[0]
     J = [d_desc_from_comp(R_d_desc[m], n) for m in range(M)]  # D x 3n
-    sqrt5 = np.sqrt(5.0)
-    U = np.empty((M, M, npm, 3 * n))
-    V = np.empty((M, M, npm, 3 * n))
-    m5 = np.empty((M, M, npm))
-    w = np.empty((M, M, npm))
+    sqrt5 = _sqrt5(dtype)
+    U = np.empty((M, M, npm, 3 * n), dtype=dtype)
+    V = np.empty((M, M, npm, 3 * n), dtype=dtype)
+    m5 = np.empty((M, M, npm), dtype=dtype)
+    w = np.empty((M, M, npm), dtype=dtype)
     for i in range(M):
         for j in range(M):
             for p in range(npm):
@@ -208,41 +222,42 @@ def pair_records(R_desc, R_d_desc, perms, sig):
                 m = np.exp(-norm / sig) * 5.0 / (3.0 * sig ** 4)
                 m5[i, j, p], w[i, j, p] = 5.0 * m, (sig ** 2 + sig * norm) * m
                 U[i, j, p] = J[i].T @ diff
-                dp = np.empty(D)
+                dp = np.empty(D, dtype=dtype)
                 dp[P[p]] = diff               # P_p^T diff
                 V[i, j, p] = J[j].T @ dp
     return U, V, m5, w
 
 
-def kernel_matvec_factored(R_desc, R_d_desc, perms, sig, x, records=None):
+def kernel_matvec_factored(R_desc, R_d_desc, perms, sig, x, records=None, dtype=np.float64):
     """The operator above regrouped as the GPU's record-factored form evaluates it
     (kernels_mf.hip k_rec_g / k_rec_fin):
         c_ijp = 5 m (v_ijp . x_j)          (= 5 m (diff . z_j[P_p]))
         G_i   = sum_jp w_ijp z_j[P_p]
         y_i   = sum_jp c_ijp u_ijp - J_i^T G_i      (= J_i^T F_i)
     Same products as kernel_matvec_matrix_free, other grouping."""
-    R_desc = np.asarray(R_desc, dtype=np.float64)
+    sig, R_desc, R_d_desc = _typed(dtype, sig, R_desc, R_d_desc)
     M, D = R_desc.shape
     n = int((1 + np.sqrt(8 * D + 1)) / 2)
     P = np.array([desc_perm(p) for p in np.atleast_2d(perms)])
-    U, V, m5, w = records if records is not None else pair_records(R_desc, R_d_desc, perms, sig)
+    U, V, m5, w = (records if records is not None
+                   else pair_records(R_desc, R_d_desc, perms, sig, dtype=dtype))
     s_at, t_at = np.tril_indices(n, k=-1)
-    X = np.asarray(x, dtype=np.float64).reshape(M, n, 3)
+    X = np.asarray(x, dtype=dtype).reshape(M, n, 3)
     z = np.einsum("mdc,mdc->md", R_d_desc, X[:, t_at, :] - X[:, s_at, :])
     Zt = z[:, P]                                    # M x n_perms x D
-    y = np.empty((M, 3 * n))
+    y = np.empty((M, 3 * n), dtype=dtype)
     for i in range(M):
         c = m5[i] * np.einsum("jpa,ja->jp", V[i], X.reshape(M, 3 * n))
         G = np.einsum("jp,jpd->d", w[i], Zt)
         contrib = R_d_desc[i] * G[:, None]
-        jtg = np.zeros((n, 3))
+        jtg = np.zeros((n, 3), dtype=dtype)
         np.add.at(jtg, t_at, contrib)
         np.add.at(jtg, s_at, -contrib)
         y[i] = np.einsum("jp,jpa->a", c, U[i]) - jtg.reshape(-1)
     return y.reshape(-1)
 
 
-def kernel_diag(R_desc, R_d_desc, perms, sig, use_E_cstr=False):
+def kernel_diag(R_desc, R_d_desc, perms, sig, use_E_cstr=False, dtype=np.float64):
     """diag(K) of the assembled sGDML kernel, one diagonal block K[i, i] per training point
     (IterativeCholesky._assemble_kernel_mat_diag, iterative_cholesky.py:241-373, which
     returns -diag for the PSD operator -K).  The block is
@@ -252,35 +267,34 @@ def kernel_diag(R_desc, R_d_desc, perms, sig, use_E_cstr=False):
     forming the D x 3n Jacobian (the nanotube's is 68265 x 1110).
     use_E_cstr: the M energy entries K[E_i, E_i] = -sum_p K_ee(|Rd_i - Rd_i[P_p]|) of
     train.py:232-234 appended."""
-    R_desc = np.asarray(R_desc, dtype=np.float64)
-    R_d_desc = np.asarray(R_d_desc, dtype=np.float64)
+    sig, R_desc, R_d_desc = _typed(dtype, sig, R_desc, R_d_desc)
     M, D = R_desc.shape
     n = int((1 + np.sqrt(8 * D + 1)) / 2)
     perms = np.atleast_2d(perms)
     if use_E_cstr:
         P = np.array([desc_perm(p) for p in perms])
-        norm = np.sqrt(5.0) * np.linalg.norm(R_desc[:, None, :] - R_desc[:, P], axis=2)  # M x n_perms
+        norm = _sqrt5(dtype) * np.linalg.norm(R_desc[:, None, :] - R_desc[:, P], axis=2)  # M x n_perms
         kee = ((1 + (norm / sig) * (1 + norm / (3 * sig))) * np.exp(-norm / sig)).sum(axis=1)
-        return np.concatenate([kernel_diag(R_desc, R_d_desc, perms, sig), -kee])
+        return np.concatenate([kernel_diag(R_desc, R_d_desc, perms, sig, dtype=dtype), -kee])
     s_at, t_at = np.tril_indices(n, k=-1)
-    out = np.empty((M, n, 3))
+    out = np.empty((M, n, 3), dtype=dtype)
     if perms.shape[0] == 1 and np.array_equal(perms[0], np.arange(n)):
         for i in range(M):
             sq = R_d_desc[i] ** 2                       # D x 3, each pair feeds both atoms
-            acc = np.zeros((n, 3))
+            acc = np.zeros((n, 3), dtype=dtype)
             np.add.at(acc, t_at, sq)
             np.add.at(acc, s_at, sq)
             out[i] = -(5.0 / (3.0 * sig ** 2)) * acc
         return out.reshape(-1)
     P = np.array([desc_perm(p) for p in perms])
-    sqrt5 = np.sqrt(5.0)
+    sqrt5 = _sqrt5(dtype)
     for i in range(M):
         J = d_desc_from_comp(R_d_desc[i], n)            # D x 3n
         diff = R_desc[i][None, :] - R_desc[i][P]        # n_perms x D
         norm = sqrt5 * np.linalg.norm(diff, axis=1)
         m = np.exp(-norm / sig) * 5.0 / (3.0 * sig ** 4)
         w = (sig ** 2 + sig * norm) * m
-        O = np.zeros((D, 3 * n))
+        O = np.zeros((D, 3 * n), dtype=dtype)
         for p in range(P.shape[0]):
             Jp = J[P[p]]                                # rows permuted: J_i[P_p]
             O += 5.0 * m[p] * np.outer(diff[p], diff[p] @ Jp) - w[p] * Jp
@@ -288,24 +302,24 @@ def kernel_diag(R_desc, R_d_desc, perms, sig, use_E_cstr=False):
     return out.reshape(-1)
 
 
-def energies_matrix_free(R_desc, R_d_desc, perms, sig, alphas):
+def energies_matrix_free(R_desc, R_d_desc, perms, sig, alphas, dtype=np.float64):
     """Training-set energies of the model with coefficients alphas, E_F[0] of
     GDMLPredict's _predict_wkr (predict.py:172-220) before the std scale and the
     integration constant: E_i = sum_jp a_ijp (sig + norm) exp(-norm/sig) 5/(3 sig^3),
     a_ijp = (Rd_i - Rd_j[P_p]) . (J_j alpha_j)[P_p], norm = sqrt5 |Rd_i - Rd_j[P_p]|."""
-    R_desc = np.asarray(R_desc, dtype=np.float64)
+    sig, R_desc, R_d_desc = _typed(dtype, sig, R_desc, R_d_desc)
     M, D = R_desc.shape
     n = int((1 + np.sqrt(8 * D + 1)) / 2)
     perms = np.atleast_2d(perms)
     P = np.array([desc_perm(p) for p in perms])
     s_at, t_at = np.tril_indices(n, k=-1)
-    A = np.asarray(alphas, dtype=np.float64).reshape(M, n, 3)
+    A = np.asarray(alphas, dtype=dtype).reshape(M, n, 3)
     z = np.einsum("mdc,mdc->md", R_d_desc, A[:, t_at, :] - A[:, s_at, :])
     Rt, Zt = R_desc[:, P], z[:, P]
-    E = np.empty(M)
+    E = np.empty(M, dtype=dtype)
     for i in range(M):
         diff = R_desc[i][None, None, :] - Rt
-        norm = np.sqrt(5.0) * np.linalg.norm(diff, axis=2)
+        norm = _sqrt5(dtype) * np.linalg.norm(diff, axis=2)
         base = np.exp(-norm / sig) * 5.0 / (3.0 * sig ** 3) * (norm + sig)
         a = np.einsum("jpd,jpd->jp", diff, Zt)
         E[i] = np.sum(a * base)
