@@ -50,20 +50,35 @@ struct DevState {
 // workgroups evaluate their tiles' entries from the points -- the stored bits -- instead of
 // streaming them, on the fp64 pipe the stream leaves idle.
 constexpr int kSymGenMaxD = 3;  // point dimensions the role keeps in registers (above: all streamed)
-// whole tiles per ms of the two roles running side by side on one MI355X, one streaming and
-// one generating workgroup per CU, d = 3 (DESIGN.md 3.1 has the sweep they come from): the
-// static share is n_s = nwhole R_s / (R_s + R_g).  The same style of modelled rates as the
-// storage choice of resolve_storage (api.hip).
-constexpr double kSymStreamRate = 2550.0;
-constexpr double kSymGenRate = 2060.0;
+// The static share n_s = nwhole R_s / (R_s + R_g) of the two roles, one streaming and one
+// generating workgroup on every CU of one MI355X, d = 3.  Since a workgroup that is done goes
+// on with the other role's range, the share only says where each role starts: R_s and R_g are
+// the units per ms at which the kernel finishes when the whole range is the streaming role's
+// ("0:2" of tools/sweep_symgen.py: 8256 tiles in 1.654 ms) and when it is the generating
+// role's ("8192:2": 1.655 ms).  They are equal, so half of the whole tiles start in either
+// role, which is the sweep's minimum (profiles/symroles/, DESIGN.md 3.1: side by side the
+// roles themselves run at 3140 and 1790 tiles/ms, but a tail left to the generating role is
+// finished at 0.14 ms per tile and workgroup, one left to the streaming role at 0.08 ms).
+constexpr double kSymStreamRate = 4990.0;
+constexpr double kSymGenRate = 4990.0;
 struct SymGen {
   const double *Xs = nullptr;
   int d = 0;
   double jitter = 0.0;
   int64_t N = 0, rows_per = 0, blk = 0;
   int n_s = 0;    // whole tiles [0, n_s) are streamed, [n_s, nwhole) generated
-  int qmode = 0;  // quarter units: 0 either role, 1 all streamed, 2 all generated
+  int qmode = 0;  // quarter units: 0 either role, 1 the streaming role's, 2 the generating role's
+  int roles = 0;  // how a workgroup gets its role (SymRoles, MLFF_SYM_ROLES)
+  int pool_first = 0;  // a role done with its own range: 0 the other role's range, then the
+                       // quarter units; 1 the quarter units first (MLFF_SYM_STEAL=pool)
 };
+// A workgroup's role: by its arrival count on its CU (even streams, odd generates: one of each
+// on every CU whatever the dispatcher's placement), by the parity of blockIdx.x (the first
+// rule, A/B), or every workgroup in one role (tests).  The result does not depend on it.
+enum SymRoles : int { kSymRolesCu = 0, kSymRolesIndex = 1, kSymRolesStream = 2, kSymRolesGen = 3 };
+// per-CU arrival words of k_symv_dyn behind its work counters: indexed by XCC id (4 bits) and
+// HW_ID bits [15:8] (CU, SH, SE), never reset (parity is all that is read)
+constexpr int kSymCuWords = 4096;
 
 // Lower-block-triangle tiles of K owned by this rank (kernels_sym.hip).
 struct SymPack {

@@ -25,9 +25,9 @@
 // order -> the result is bitwise deterministic.
 //
 // Tiles that were generated from the RBF points (k_sym_gen_rbf) need not all be read
-// again: in k_symv_dyn<true> half of the resident workgroups evaluate the entries of their
-// tiles from the points (the stored bits) on the fp64 pipe that the stream leaves idle,
-// while the other half streams.
+// again: in k_symv_dyn<true> one of the two resident workgroups of every CU evaluates the
+// entries of its tiles from the points (the stored bits) on the fp64 pipe that the stream
+// leaves idle, while the other one streams.
 #include "common.h"
 
 #include <algorithm>
@@ -129,7 +129,8 @@ __device__ __forceinline__ double fused_p_beta(const PGather &pg, double rho, do
 // Work counters of k_symv_dyn (sp.ticket): [0] the streaming role's whole tiles (every unit
 // when nothing is generated), [1] k_sym_reduce_w's arrival counter, [2] the generating role's
 // whole tiles, [3] the quarter units either role takes once its own range is exhausted.
-// Every slot reduction resets the three work counters for the next launch.
+// Every slot reduction resets the three work counters for the next launch.  Behind them the
+// kSymCuWords per-CU arrival words of the role rule (zeroed at allocation, never reset).
 constexpr int kTicketWords = 4;
 __device__ __forceinline__ void reset_work_counters(unsigned long long *ticket) {
   ticket[0] = 0ull;
@@ -137,19 +138,38 @@ __device__ __forceinline__ void reset_work_counters(unsigned long long *ticket) 
   ticket[3] = 0ull;
 }
 
-// next unit of a role (thread 0): its own range [.., hi) through its counter (base = the
-// range's start + the role's workgroups, which took their first unit without an atomic),
-// then -- where the role may -- the shared quarter units; >= nunits: nothing left.  Nobody
-// waits for anybody: a wrong count gives a wrong sum, never a hang.
-__device__ __forceinline__ long long next_unit(unsigned long long *own, long long base, long long hi,
-                                               bool pool, unsigned long long *shared, int nwhole,
-                                               long long nunits, bool &own_done) {
-  if (!own_done) {
-    const long long u = base + (long long)atomicAdd(own, 1ull);
-    if (u < hi) return u;
-    own_done = true;
+// The unit ranges a workgroup takes from, in its order: range r is [base_r + count, hi_r)
+// through counter c_r.  A role's first range is its own; the others are the other role's whole
+// tiles and the quarter units, so every range is finished however many workgroups hold either
+// role (all of them in one role included).
+struct UnitQueue {
+  unsigned long long *c0, *c1, *c2;
+  long long base0, hi0, base1, hi1, base2, hi2;
+  int stage;
+};
+__device__ __forceinline__ bool take_unit(unsigned long long *c, long long base, long long hi,
+                                          long long &u) {
+  if (base >= hi) return false;
+  u = base + (long long)atomicAdd(c, 1ull);
+  return u < hi;
+}
+// next unit (thread 0); >= nunits: nothing left.  Nobody waits for anybody: a wrong count
+// gives a wrong sum, never a hang.
+__device__ __forceinline__ long long next_unit(UnitQueue &q, long long nunits) {
+  long long u;
+  if (q.stage == 0) {
+    if (take_unit(q.c0, q.base0, q.hi0, u)) return u;
+    q.stage = 1;
   }
-  return pool ? nwhole + (long long)atomicAdd(shared, 1ull) : nunits;
+  if (q.stage == 1) {
+    if (take_unit(q.c1, q.base1, q.hi1, u)) return u;
+    q.stage = 2;
+  }
+  if (q.stage == 2) {
+    if (take_unit(q.c2, q.base2, q.hi2, u)) return u;
+    q.stage = 3;
+  }
+  return nunits;
 }
 
 // global index of padded position pos (k_sym_gen_rbf's mapping); false: padding (K is zero)
@@ -381,10 +401,8 @@ struct SymvArgs {
 // out at their two places each: as helpers they are scheduled differently, 2 VGPRs more.)
 template <bool GEN>
 __device__ __forceinline__ long long symv_units(const SymvArgs &k, const SymGen &gs, long long u,
-                                                unsigned long long *own, long long base,
-                                                long long hi, bool pool,
-                                                unsigned long long *shared, bool own_done,
-                                                double *__restrict__ sh, long long *s_next) {
+                                                UnitQueue q, double *__restrict__ sh,
+                                                long long *s_next) {
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   double *vrow = sh, *rows = sh + B, *cs = sh + 2 * B;
   double *red = sh + kTileRed + w * kRB * 64;
@@ -402,7 +420,7 @@ __device__ __forceinline__ long long symv_units(const SymvArgs &k, const SymGen 
 #pragma unroll
   for (int q = 0; q < 4; ++q) pc[q] = pg_val2(pg, v, (int64_t)t.y * B + 2 * (lane + 64 * q), beta);
   if constexpr (!GEN) tile_load_batch(A, (int64_t)(gb0 + w) * kRB, lane, a);
-  if (threadIdx.x == 0) *s_next = next_unit(own, base, hi, pool, shared, k.nwhole, k.nunits, own_done);
+  if (threadIdx.x == 0) *s_next = next_unit(q, k.nunits);
   for (int i = threadIdx.x; i < (gb1 - gb0) * kRB; i += 256) {
     const int64_t gi = (int64_t)t.x * B + gb0 * kRB + i;
     vrow[gb0 * kRB + i] = pg.gb != nullptr ? pg_val(pg, v, gi, beta) : v[gi];
@@ -446,7 +464,7 @@ __device__ __forceinline__ long long symv_units(const SymvArgs &k, const SymGen 
     __syncthreads();  // LDS consumed, s_next read by everyone
     ++units_done;
     if (un >= k.nunits) break;
-    if (threadIdx.x == 0) *s_next = next_unit(own, base, hi, pool, shared, k.nwhole, k.nunits, own_done);
+    if (threadIdx.x == 0) *s_next = next_unit(q, k.nunits);
     tile = tile2;
     h = h2;
     gb0 = gb02;
@@ -463,11 +481,28 @@ __device__ __forceinline__ long long symv_units(const SymvArgs &k, const SymGen 
   return units_done;
 }
 
+// The CU a workgroup runs on as an index below kSymCuWords: the XCC id and HW_ID bits [15:8]
+// (gfx9: CU_ID [11:8], SH_ID [12], SE_ID from bit 13)
+__device__ __forceinline__ unsigned cu_key() {
+  unsigned xcc = 0, hw = 0;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+  return ((xcc & 0xfu) << 8) | ((hw >> 8) & 0xffu);
+}
+
+// MLFF_SYM_TRACE record of a workgroup: start, end, units taken, 1 | role << 1 | CU key << 2
+constexpr int kTraceWords = 4;
+
 // ROLES false: every workgroup streams, one counter over all units (sp.gen off: matrices set
-// by the host, MLFF_SYM_GEN=0, d above kSymGenMaxD).  ROLES true (tiles generated from the
-// RBF points): even workgroups stream the stored whole tiles [0, gs.n_s), odd ones evaluate
-// the whole tiles [gs.n_s, nwhole) from the points instead of reading them; the quarter units
-// go to whoever is done first (gs.qmode 0), to the streaming (1) or the generating role (2).
+// by the host, MLFF_SYM_GEN=0, d above kSymGenMaxD); the first unit is blockIdx.x, without an
+// atomic.  ROLES true (tiles generated from the RBF points): a streaming workgroup reads the
+// stored whole tiles [0, gs.n_s), a generating one evaluates the whole tiles [gs.n_s, nwhole)
+// from the points; the quarter units are a third range, either role's (gs.qmode 0), the
+// streaming (1) or the generating role's (2).  The role comes from the order of arrival on the
+// CU (gs.roles), so the dispatcher's placement cannot put two of a kind on one CU and none on
+// another; it is therefore not known at launch how many workgroups hold a role, and every unit,
+// the first included, comes from a counter.  A workgroup done with its role's ranges goes on
+// with the other role's, in its own manner (the bits are the same, tile_batch<GEN>).
 template <bool ROLES>
 __global__ __launch_bounds__(256) void k_symv_dyn(const double *__restrict__ tiles,
                                                   const int2 *__restrict__ list,
@@ -481,49 +516,68 @@ __global__ __launch_bounds__(256) void k_symv_dyn(const double *__restrict__ til
                                                   SymGen gs,
                                                   unsigned long long *wgtrace = nullptr) {
   if (status != nullptr && *status != ST_RUNNING) return;
-  // MLFF_SYM_TRACE (diagnostic): per workgroup its start, end and units taken
-  if (wgtrace != nullptr && threadIdx.x == 0) wgtrace[3 * blockIdx.x] = wall_clock64();
+  // MLFF_SYM_TRACE (diagnostic): per workgroup its start, end, units taken, role and CU
+  unsigned long long *tr = wgtrace != nullptr ? wgtrace + kTraceWords * blockIdx.x : nullptr;
+  if (tr != nullptr && threadIdx.x == 0) tr[0] = wall_clock64();
   __shared__ double sh[kTileLds + (ROLES ? 4 * B : 0)];
   __shared__ long long s_next;
-  // first unit = the workgroup's index in its role (no atomic burst at launch: one counter
-  // word serves ~90 grabs per us); later grabs come from the counter, offset by the role's
-  // workgroups
-  const bool gen = ROLES && (blockIdx.x & 1u);
-  const long long G = !ROLES ? (long long)gridDim.x : gen ? gridDim.x / 2 : (gridDim.x + 1) / 2;
-  const long long idx = ROLES ? blockIdx.x >> 1 : blockIdx.x;
-  const long long lo = gen ? gs.n_s : 0;
-  const long long hi = !ROLES ? nunits : gen ? nwhole : gs.n_s;
-  const bool pool = ROLES && gs.qmode != (gen ? 1 : 2);
-  if (!ROLES && idx >= nunits) return;
+  __shared__ int s_role;
+  if (!ROLES && (long long)blockIdx.x >= nunits) return;
+  if (ROLES && threadIdx.x == 0) {
+    int r = gs.roles == kSymRolesGen ? 1 : 0;
+    if (gs.roles == kSymRolesIndex) r = (int)(blockIdx.x & 1u);
+    if (gs.roles == kSymRolesCu) r = (int)(atomicAdd(ticket + kTicketWords + cu_key(), 1ull) & 1ull);
+    s_role = r;
+  }
+  if (!ROLES && tr != nullptr && threadIdx.x == 0) tr[3] = 1ull | (unsigned long long)cu_key() << 2;
   const double beta = pg.gb != nullptr ? fused_p_beta(pg, gathered_rho(pg, sh), &pg.st->rho_new) : 0.0;
-  long long u = lo + idx;
-  bool own_done = false;
-  if (ROLES) {  // a role with fewer whole tiles than workgroups starts in the shared units
+  UnitQueue q{ticket, ticket, ticket, (long long)gridDim.x, nunits, 0, 0, 0, 0, 0};
+  long long u = blockIdx.x;
+  bool gen = false;
+  if (ROLES) {
+    __syncthreads();
+    gen = __builtin_amdgcn_readfirstlane(s_role) != 0;
+    // own whole tiles, then the other role's whole tiles and the quarter units: the quarters
+    // last where they are the other role's (qmode), else in the order of gs.pool_first
+    const bool pool_first = gs.pool_first != 0 && gs.qmode != (gen ? 1 : 2);
+    unsigned long long *cs = ticket, *cg = ticket + 2, *cq = ticket + 3;
+    const long long ns = gs.n_s;
+    q.c0 = gen ? cg : cs;
+    q.base0 = gen ? ns : 0;
+    q.hi0 = gen ? nwhole : ns;
+    unsigned long long *co = gen ? cs : cg;
+    const long long olo = gen ? 0 : ns, ohi = gen ? ns : nwhole;
+    q.c1 = pool_first ? cq : co;
+    q.base1 = pool_first ? nwhole : olo;
+    q.hi1 = pool_first ? nunits : ohi;
+    q.c2 = pool_first ? co : cq;
+    q.base2 = pool_first ? olo : nwhole;
+    q.hi2 = pool_first ? ohi : nunits;
     if (threadIdx.x == 0) {
-      if (u >= hi) {
-        own_done = true;
-        u = pool ? nwhole + (long long)atomicAdd(ticket + 3, 1ull) : nunits;
-      }
-      s_next = u;
+      s_next = next_unit(q, nunits);
+      if (tr != nullptr) tr[3] = 1ull | (gen ? 2ull : 0ull) | (unsigned long long)cu_key() << 2;
     }
     __syncthreads();
     u = s_next;
     __syncthreads();
-    if (u >= nunits) return;
+    if (u >= nunits) {
+      if (tr != nullptr && threadIdx.x == 0) tr[1] = wall_clock64();
+      return;
+    }
   }
   const SymvArgs k{tiles, list, v, P, Pq, Np, nwhole, nunits, nb, lsub, pg, beta};
   long long units_done;
   if constexpr (ROLES) {
     if (gen)
-      units_done = symv_units<true>(k, gs, u, ticket + 2, lo + G, hi, pool, ticket + 3, own_done, sh, &s_next);
+      units_done = symv_units<true>(k, gs, u, q, sh, &s_next);
     else
-      units_done = symv_units<false>(k, gs, u, ticket, lo + G, hi, pool, ticket + 3, own_done, sh, &s_next);
+      units_done = symv_units<false>(k, gs, u, q, sh, &s_next);
   } else {
-    units_done = symv_units<false>(k, gs, u, ticket, lo + G, hi, pool, ticket + 3, own_done, sh, &s_next);
+    units_done = symv_units<false>(k, gs, u, q, sh, &s_next);
   }
-  if (wgtrace != nullptr && threadIdx.x == 0) {
-    wgtrace[3 * blockIdx.x + 1] = wall_clock64();
-    wgtrace[3 * blockIdx.x + 2] = (unsigned long long)units_done;
+  if (tr != nullptr && threadIdx.x == 0) {
+    tr[1] = wall_clock64();
+    tr[2] = (unsigned long long)units_done;
   }
 }
 
@@ -1066,6 +1120,13 @@ struct SymKnobs {
   bool gen = true;
   int64_t gen_tiles = -1;
   int gen_quarters = 0;
+  // MLFF_SYM_ROLES=cu|index|stream|gen: a workgroup's role by its arrival count on its CU; by
+  // the parity of blockIdx.x (the first rule, A/B: the dispatcher deals blocks round-robin over
+  // the XCDs, so parity put each role on half of the chip); every workgroup
+  // streaming / generating (tests).  MLFF_SYM_STEAL=other|pool: what a workgroup whose own
+  // range is exhausted takes first, the other role's whole tiles or the quarter units.
+  int roles = kSymRolesCu;
+  int pool_first = 0;
   // MLFF_SYM_REDUCE_LIST=0: k_sym_reduce_w instead of k_sym_reduce_wl (W > 1)
   bool reduce_list = true;
   // MLFF_SYM_PQ_ORDERED=1: k_sym_reduce_wl's arrival in the formally ordered form (pq_put)
@@ -1090,6 +1151,12 @@ static SymKnobs sym_knobs() {
     const int v = std::atoi(e);
     if (v >= 0 && v <= 2) k.gen_quarters = v;
   }
+  if (const char *e = std::getenv("MLFF_SYM_ROLES")) {
+    if (std::strcmp(e, "index") == 0) k.roles = kSymRolesIndex;
+    if (std::strcmp(e, "stream") == 0) k.roles = kSymRolesStream;
+    if (std::strcmp(e, "gen") == 0) k.roles = kSymRolesGen;
+  }
+  if (const char *e = std::getenv("MLFF_SYM_STEAL")) k.pool_first = std::strcmp(e, "pool") == 0;
   if (const char *e = std::getenv("MLFF_SYM_REDUCE_LIST")) k.reduce_list = std::atoi(e) != 0;
   if (const char *e = std::getenv("MLFF_SYM_PQ_ORDERED")) k.pq_ordered = std::atoi(e) != 0;
   if (const char *e = std::getenv("MLFF_SYM_TRACE")) k.trace_at = std::atoll(e);
@@ -1097,26 +1164,39 @@ static SymKnobs sym_knobs() {
 }
 
 // MLFF_SYM_TRACE: the ramp until every workgroup runs, the tail after the median one is done
-// (tr: start, end (10-ns ticks) and units of each of the G workgroups; one sync)
+// (tr: start, end (10-ns ticks), units, role and CU of each of the G workgroups; one sync), and
+// where the dispatcher put the two roles
 static void print_symv_trace(const unsigned long long *tr, unsigned G, int64_t units, hipStream_t s) {
-  std::vector<unsigned long long> h((size_t)3 * G);
+  std::vector<unsigned long long> h((size_t)kTraceWords * G);
   if (hipStreamSynchronize(s) != hipSuccess ||
       hipMemcpy(h.data(), tr, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost) != hipSuccess)
     return;
   unsigned long long t0 = ~0ull, t1 = 0;
   std::vector<double> st, en, un;
   for (unsigned g = 0; g < G; ++g) {
-    if (h[3 * g] == 0) continue;
-    t0 = std::min(t0, h[3 * g]);
-    t1 = std::max(t1, h[3 * g + 1]);
+    const unsigned long long *r = &h[(size_t)kTraceWords * g];
+    if (r[0] == 0) continue;
+    t0 = std::min(t0, r[0]);
+    t1 = std::max(t1, r[1]);
   }
   double idle = 0.0;
+  // per CU key and per XCC id: streaming / generating workgroups seen
+  std::vector<int> cu_s(kSymCuWords, 0), cu_g(kSymCuWords, 0);
+  int xs[16] = {0}, xg[16] = {0};
+  double un_s = 0.0, un_g = 0.0;
   for (unsigned g = 0; g < G; ++g) {
-    if (h[3 * g] == 0) continue;
-    st.push_back(10.0 * (double)(h[3 * g] - t0));
-    en.push_back(10.0 * (double)(h[3 * g + 1] - t0));
-    un.push_back((double)h[3 * g + 2]);
-    idle += 10.0 * (double)(t1 - h[3 * g + 1]) + 10.0 * (double)(h[3 * g] - t0);
+    const unsigned long long *r = &h[(size_t)kTraceWords * g];
+    if (r[0] == 0) continue;
+    st.push_back(10.0 * (double)(r[0] - t0));
+    en.push_back(10.0 * (double)(r[1] - t0));
+    un.push_back((double)r[2]);
+    idle += 10.0 * (double)(t1 - r[1]) + 10.0 * (double)(r[0] - t0);
+    if (!(r[3] & 1ull)) continue;
+    const bool gen = (r[3] & 2ull) != 0;
+    const unsigned key = (unsigned)(r[3] >> 2) & (kSymCuWords - 1);
+    ++(gen ? cu_g : cu_s)[key];
+    ++(gen ? xg : xs)[key >> 8];
+    (gen ? un_g : un_s) += (double)r[2];
   }
   auto q = [](std::vector<double> v, double f) {
     std::sort(v.begin(), v.end());
@@ -1131,6 +1211,27 @@ static void print_symv_trace(const unsigned long long *tr, unsigned G, int64_t u
                1e-3 * q(st, 0.5), 1e-3 * q(st, 1.0), 1e-3 * q(en, 0.0), 1e-3 * q(en, 0.1),
                1e-3 * q(en, 0.5), 1e-3 * q(en, 0.9), 1e-3 * q(en, 1.0),
                100.0 * idle / (span * (double)st.size()));
+  int cus = 0, paired = 0, two_s = 0, two_g = 0, other = 0;
+  for (int k = 0; k < kSymCuWords; ++k) {
+    if (cu_s[k] + cu_g[k] == 0) continue;
+    ++cus;
+    if (cu_s[k] == 1 && cu_g[k] == 1)
+      ++paired;
+    else if (cu_s[k] == 2 && cu_g[k] == 0)
+      ++two_s;
+    else if (cu_s[k] == 0 && cu_g[k] == 2)
+      ++two_g;
+    else
+      ++other;
+  }
+  std::string per_xcc;
+  for (int x = 0; x < 16; ++x)
+    if (xs[x] + xg[x] > 0)
+      per_xcc += " " + std::to_string(x) + ":" + std::to_string(xs[x]) + "s+" + std::to_string(xg[x]) + "g";
+  std::fprintf(stderr,
+               "[sym trace] roles: %d distinct CU keys; CUs holding {stream + gen} %d, {2 stream} %d, "
+               "{2 gen} %d, other %d; units taken stream / gen %.0f / %.0f; per XCC id%s\n",
+               cus, paired, two_s, two_g, other, un_s, un_g, per_xcc.c_str());
 }
 
 void launch_symv(const SymPack &sp, const double *v_full, double *P, const int *status,
@@ -1147,8 +1248,8 @@ void launch_symv(const SymPack &sp, const double *v_full, double *P, const int *
   static long long launches = 0;
   unsigned long long *tr = nullptr;
   if (trace_at > 0 && ++launches == trace_at &&
-      hipMalloc(&tr, sizeof(unsigned long long) * 3 * G) == hipSuccess)
-    (void)hipMemsetAsync(tr, 0, sizeof(unsigned long long) * 3 * G, s);
+      hipMalloc(&tr, sizeof(unsigned long long) * kTraceWords * G) == hipSuccess)
+    (void)hipMemsetAsync(tr, 0, sizeof(unsigned long long) * kTraceWords * G, s);
   if (sp.gen)
     hipLaunchKernelGGL(k_symv_dyn<true>, dim3(G), dim3(256), 0, s,
                        sp.tiles, sp.list, v_full, P, sp.Pq, sp.Np, (int)sp.nwhole, (long long)grid,
@@ -1302,7 +1403,7 @@ static SymPlan sym_plan(const mlff_ctx *ctx, const SymKnobs &kn) {
     if (on) {
       pl.gen = true;
       pl.gsrc = SymGen{ctx->rbf.Xs, ctx->rbf.d, ctx->rbf.jitter, ctx->N, ctx->rows_per, ctx->blk,
-                       (int)n_s, qmode};
+                       (int)n_s, qmode, kn.roles, kn.pool_first};
     }
   }
   return pl;
@@ -1326,9 +1427,11 @@ static int sym_alloc(mlff_ctx *ctx, const SymPlan &pl, const SymKnobs &kn) {
     sp.pq_planes = nq;
     MLFF_HIP(ctx, hipMalloc(&sp.split, (size_t)nb * nb));
     MLFF_HIP(ctx, hipMalloc(&sp.own, sizeof(int) * (size_t)nb * (nb + 1)));
-    // k_symv_dyn's work counters and the rank reductions' arrival counter (kTicketWords)
-    MLFF_HIP(ctx, hipMalloc(&sp.ticket, kTicketWords * sizeof(unsigned long long)));
-    MLFF_HIP(ctx, hipMemsetAsync(sp.ticket, 0, kTicketWords * sizeof(unsigned long long), s));
+    // k_symv_dyn's work counters and the rank reductions' arrival counter (kTicketWords), then
+    // the per-CU arrival words of its role rule
+    const size_t tw = (kTicketWords + kSymCuWords) * sizeof(unsigned long long);
+    MLFF_HIP(ctx, hipMalloc(&sp.ticket, tw));
+    MLFF_HIP(ctx, hipMemsetAsync(sp.ticket, 0, tw, s));
     if (ctx->world > 1) {
       // reduce-scatter operand: rank blocks of blk rows + a tail of p.q shares
       sp.ystride = ctx->blk + round_up(ctx->world, kPad);
