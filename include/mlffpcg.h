@@ -241,6 +241,10 @@ int mlff_sym_min_eig(mlff_ctx *ctx, const double *M, int64_t m, double *lo_eig_o
                      double *d_out, double *e_out);
 int mlff_sgdml_descriptors(const double *R, int64_t M, int n_atoms, double *R_desc_out,
                            double *R_d_desc_out);
+/* The RBF entry exp(-0.5 s) of n host squared distances s, evaluated on the device twice: by
+ * the device library's exp (the stored tiles, rows and columns) into lib_out and by the
+ * select-free form of the tile mat-vec's generating role into lean_out.  Test hook. */
+int mlff_test_rbf_exp(mlff_ctx *ctx, const double *s, int64_t n, double *lib_out, double *lean_out);
 
 /* operator A = sigma_K * K + lam * I.  sGDML: sigma_K = -1 (K is negative
  * semidefinite, the solved system is (-K + lam I) x = y, iterative_solver.py:995);
@@ -301,6 +305,13 @@ int mlff_set_storage(mlff_ctx *ctx, int mode);
  * whichever role is free first and count as streamed, so the figure is an upper
  * bound by less than one quarter tile per resident workgroup. */
 int mlff_storage_info(mlff_ctx *ctx, int *mode_out, double *bytes_per_matvec_out);
+/* The persistent launch of the symmetric tile mat-vec (MLFF_STORAGE_SYMTILE, else
+ * MLFF_ERR_STATE): the workgroups resident on one CU at once and the workgroups launched
+ * (that number times the CUs).  Tiles generated from RBF points run three per CU, one
+ * streaming and two generating -- the runtime's occupancy query for that kernel, not a
+ * constant -- where the rank has at least two work units per workgroup (MLFF_SYM_WGS=3:
+ * always; =2: never); every other tile operator runs two. */
+int mlff_sym_launch_info(mlff_ctx *ctx, int *wgs_per_cu_out, int64_t *grid_out);
 /* form of the matrix-free sGDML operator (MLFF_STORAGE_MATFREE; the reference's K_op,
  * iterative_solver.py:383-445 / predict.py:172-220, evaluated three ways):
  * MLFF_MF_FORM_PAIR (pair sums, then F, then J^T), MLFF_MF_FORM_REC (record-factored: x-independent

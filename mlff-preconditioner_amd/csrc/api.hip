@@ -1620,6 +1620,26 @@ int mlff_set_energy_constraints(mlff_ctx *ctx, int use_E_cstr) {
   MLFF_API_END(ctx)
 }
 
+int mlff_test_rbf_exp(mlff_ctx *ctx, const double *s, int64_t n, double *lib_out, double *lean_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  if (s == nullptr || lib_out == nullptr || lean_out == nullptr || n < 1)
+    return set_error(ctx, MLFF_ERR_ARG, "test_rbf_exp: bad arguments");
+  ScratchScope scope(ctx);
+  double *ds = nullptr, *da = nullptr, *db = nullptr;
+  MLFF_TRY(scratch_alloc(ctx, &ds, (size_t)n));
+  MLFF_TRY(scratch_alloc(ctx, &da, (size_t)n));
+  MLFF_TRY(scratch_alloc(ctx, &db, (size_t)n));
+  MLFF_HIP(ctx, hipMemcpyAsync(ds, s, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
+  launch_rbf_exp_probe(ds, n, da, db, ctx->stream);
+  MLFF_HIP(ctx, hipGetLastError());
+  MLFF_HIP(ctx, hipMemcpyAsync(lib_out, da, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  MLFF_HIP(ctx, hipMemcpyAsync(lean_out, db, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
+  MLFF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return MLFF_OK;
+  MLFF_API_END(ctx)
+}
+
 int mlff_sgdml_descriptors(const double *R, int64_t M, int n_atoms, double *R_desc_out,
                            double *R_d_desc_out) {
   MLFF_API_BEGIN
@@ -1743,6 +1763,18 @@ int mlff_storage_info(mlff_ctx *ctx, int *mode_out, double *bytes_per_matvec_out
     *mode_out = ctx->use_mf ? MLFF_STORAGE_MATFREE
                             : (ctx->use_sym ? MLFF_STORAGE_SYMTILE : MLFF_STORAGE_DENSE);
   if (bytes_per_matvec_out) *bytes_per_matvec_out = operator_bytes(ctx);
+  return MLFF_OK;
+  MLFF_API_END(ctx)
+}
+
+int mlff_sym_launch_info(mlff_ctx *ctx, int *wgs_per_cu_out, int64_t *grid_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  MLFF_TRY(require_operator(ctx));
+  MLFF_TRY(resolve_storage(ctx));
+  if (!ctx->use_sym || !ctx->sym.ready) return set_error(ctx, MLFF_ERR_STATE, "no symmetric tile operator");
+  if (wgs_per_cu_out) *wgs_per_cu_out = ctx->sym.wgs;
+  if (grid_out) *grid_out = ctx->sym.dyn;
   return MLFF_OK;
   MLFF_API_END(ctx)
 }

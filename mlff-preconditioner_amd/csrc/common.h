@@ -50,17 +50,21 @@ struct DevState {
 // workgroups evaluate their tiles' entries from the points -- the stored bits -- instead of
 // streaming them, on the fp64 pipe the stream leaves idle.
 constexpr int kSymGenMaxD = 3;  // point dimensions the role keeps in registers (above: all streamed)
-// The static share n_s = nwhole R_s / (R_s + R_g) of the two roles, one streaming and one
-// generating workgroup on every CU of one MI355X, d = 3.  Since a workgroup that is done goes
+// The static share n_s = nwhole R_s / (R_s + R_g) of the two roles, one streaming and two
+// generating workgroups on every CU of one MI355X, d = 3.  Since a workgroup that is done goes
 // on with the other role's range, the share only says where each role starts: R_s and R_g are
 // the units per ms at which the kernel finishes when the whole range is the streaming role's
-// ("0:2" of tools/sweep_symgen.py: 8256 tiles in 1.654 ms) and when it is the generating
-// role's ("8192:2": 1.655 ms).  They are equal, so half of the whole tiles start in either
-// role, which is the sweep's minimum (profiles/symroles/, DESIGN.md 3.1: side by side the
-// roles themselves run at 3140 and 1790 tiles/ms, but a tail left to the generating role is
-// finished at 0.14 ms per tile and workgroup, one left to the streaming role at 0.08 ms).
-constexpr double kSymStreamRate = 4990.0;
-constexpr double kSymGenRate = 4990.0;
+// ("0:2" of tools/sweep_symgen.py: 8256 tiles in 1.47 ms, the step's 1.540 less the 0.07 ms
+// of its other kernels) and when it is the generating role's ("8192:2": 1.48 ms).  They are
+// equal within the timings' scatter, so half of the whole tiles start in either role; the
+// sweep is flat within 1.5 % from 4096 to 7168 generated tiles (profiles/symlean/, DESIGN.md
+// 3.1: side by side the roles themselves run at 2700 and 2960 tiles/ms and end up with 48 and
+// 52 % of the units).
+constexpr double kSymStreamRate = 5600.0;
+constexpr double kSymGenRate = 5600.0;
+// units per resident workgroup from which the three-workgroup form runs (below: two workgroups
+// per CU; measured at 1.4, where it loses, and at 2.75, 5.5 and 11, where it wins)
+constexpr int kSymThreeWgMinUnits = 2;
 struct SymGen {
   const double *Xs = nullptr;
   int d = 0;
@@ -71,13 +75,15 @@ struct SymGen {
   int roles = 0;  // how a workgroup gets its role (SymRoles, MLFF_SYM_ROLES)
   int pool_first = 0;  // a role done with its own range: 0 the other role's range, then the
                        // quarter units; 1 the quarter units first (MLFF_SYM_STEAL=pool)
+  int wgs = 2;    // resident workgroups per CU: one of them streams, the others generate
 };
-// A workgroup's role: by its arrival count on its CU (even streams, odd generates: one of each
-// on every CU whatever the dispatcher's placement), by the parity of blockIdx.x (the first
-// rule, A/B), or every workgroup in one role (tests).  The result does not depend on it.
+// A workgroup's role: by its arrival count on its CU (of every SymGen::wgs arrivals the first
+// streams, the others generate: one streaming workgroup on every CU whatever the dispatcher's
+// placement), by blockIdx.x in the same way (the first rule, A/B), or every workgroup in one
+// role (tests).  The result does not depend on it.
 enum SymRoles : int { kSymRolesCu = 0, kSymRolesIndex = 1, kSymRolesStream = 2, kSymRolesGen = 3 };
 // per-CU arrival words of k_symv_dyn behind its work counters: indexed by XCC id (4 bits) and
-// HW_ID bits [15:8] (CU, SH, SE), never reset (parity is all that is read)
+// HW_ID bits [15:8] (CU, SH, SE), never reset (the count modulo SymGen::wgs is all that is read)
 constexpr int kSymCuWords = 4096;
 
 // Lower-block-triangle tiles of K owned by this rank (kernels_sym.hip).
@@ -108,6 +114,8 @@ struct SymPack {
   bool pq_ordered = false;         // k_sym_reduce_wl's arrival ordered (MLFF_SYM_PQ_ORDERED=1)
   int64_t t_split = 0;             // smallest I of a split tile (nb if none)
   int64_t dyn = 0;                 // > 0: k_symv_dyn with this many workgroups
+  int wgs = 0;                     // ... which is this many resident workgroups on every CU
+  bool rb4 = false;                // the three-workgroup form (k_symv_dyn<true, 4>, MLFF_SYM_WGS)
   unsigned long long *ticket = nullptr;  // its work counters (reset by the slot reduction)
   bool gen = false;                // k_symv_dyn with a generating role (RBF source, sym_build)
   SymGen gsrc;                     // its source and the share of the two roles
@@ -227,6 +235,35 @@ __device__ __forceinline__ double rbf_sqdist_step(double s, double df, bool firs
   return first ? __dmul_rn(df, df) : fma(df, df, s);
 }
 __device__ __forceinline__ double rbf_of_sqdist(double s) { return exp(-0.5 * s); }
+// rbf_of_sqdist for the tile mat-vec's generating role: the device library's exp written out --
+// its constants and its order of operations (x log2e rounded to n, x - n ln2 in two fma, the
+// degree-11 polynomial, ldexp by n) -- without its two range selects.  `x > 1024 ? inf` cannot
+// fire for x = -0.5 s <= 0; `x < -1075 ? 0` is replaced by clamping x at -1075 first: there n =
+// -1551 and ldexp gives +0, the select's value, and above it the select does nothing.  Domain:
+// finite points, so s >= 0 or s = +inf (never NaN).  On that domain the bits are exp's
+// (tests/test_gpu_rbf_exp_lean.py compares the two on the device); the kernels that store
+// tiles, rows and columns keep calling exp, so no stored value can depend on this.
+__device__ __forceinline__ double rbf_exp_c(unsigned long long bits) {
+  return __builtin_bit_cast(double, bits);
+}
+__device__ __forceinline__ double rbf_of_sqdist_lean(double s) {
+  const double x = __builtin_fmax(-0.5 * s, -1075.0);
+  const double n = __builtin_rint(__dmul_rn(x, rbf_exp_c(0x3FF71547652B82FEull)));
+  double r = fma(-n, rbf_exp_c(0x3FE62E42FEFA39EFull), x);
+  r = fma(-n, rbf_exp_c(0x3C7ABC9E3B39803Full), r);
+  double p = fma(r, rbf_exp_c(0x3E5ADE156A5DCB37ull), rbf_exp_c(0x3E928AF3FCA7AB0Cull));
+  p = fma(r, p, rbf_exp_c(0x3EC71DEE623FDE64ull));
+  p = fma(r, p, rbf_exp_c(0x3EFA01997C89E6B0ull));
+  p = fma(r, p, rbf_exp_c(0x3F2A01A014761F6Eull));
+  p = fma(r, p, rbf_exp_c(0x3F56C16C1852B7B0ull));
+  p = fma(r, p, rbf_exp_c(0x3F81111111122322ull));
+  p = fma(r, p, rbf_exp_c(0x3FA55555555502A1ull));
+  p = fma(r, p, rbf_exp_c(0x3FC5555555555511ull));
+  p = fma(r, p, rbf_exp_c(0x3FE000000000000Bull));
+  p = fma(r, p, 1.0);
+  p = fma(r, p, 1.0);
+  return __builtin_ldexp(p, (int)n);
+}
 __device__ __forceinline__ double rbf_value(const double (&xi)[8], const double *__restrict__ Xs,
                                             int64_t g, int d) {
   double s = 0.0;
@@ -814,6 +851,9 @@ struct PGather {
   DevState *st = nullptr;
   long long it = 0;
 };
+// test hook: lib_out[i] = rbf_of_sqdist(s[i]), lean_out[i] = rbf_of_sqdist_lean(s[i]) (device arrays)
+void launch_rbf_exp_probe(const double *s, int64_t n, double *lib_out, double *lean_out,
+                          hipStream_t st);
 // P <- slot partials of K v_full over the stored tiles
 void launch_symv(const SymPack &sp, const double *v_full, double *P, const int *status,
                  hipStream_t s, PGather pg = PGather{});

@@ -25,9 +25,9 @@
 // order -> the result is bitwise deterministic.
 //
 // Tiles that were generated from the RBF points (k_sym_gen_rbf) need not all be read
-// again: in k_symv_dyn<true> one of the two resident workgroups of every CU evaluates the
-// entries of its tiles from the points (the stored bits) on the fp64 pipe that the stream
-// leaves idle, while the other one streams.
+// again: in k_symv_dyn<true> two of the three resident workgroups of every CU evaluate the
+// entries of their tiles from the points (the stored bits) on the fp64 pipe that the stream
+// leaves idle, while the third one streams.
 #include "common.h"
 
 #include <algorithm>
@@ -47,6 +47,10 @@ constexpr int kBatches = B / kRB;  // 8-row batches per tile
 // partials | the 4 waves' private kRB x 64 transpose buffers (| the generating role's row points)
 constexpr int kTileRed = 6 * B;  // the transpose buffers' offset
 constexpr int kTileLds = kTileRed + 4 * kRB * 64;
+// the generating role's row points behind them: 3 doubles per row, then one bit per row (inside
+// [0, N) / padding) in B / 32 words.  53,328 bytes in all: three workgroups fit the CU's 160 KB
+// (allocated in units of 1280 bytes, so at most 53,760 each)
+constexpr int kGenRowLds = kSymGenMaxD * B + B / 64;
 
 // Work units: [0, nwhole) one whole tile each, then 2^lsub units per remaining tile, one row
 // slice (512 >> lsub rows, batches [gb0, gb1)) each, so a launch ends on sub-tile units instead
@@ -197,17 +201,28 @@ __device__ __forceinline__ void gen_load_cols(const SymGen &gs, int J, int lane,
     for (int t = 0; t < kSymGenMaxD; ++t) gc.x[j][t] = (ok && t < gs.d) ? gs.Xs[g * gs.d + t] : 0.0;
   }
 }
-// row points of rows [r0, r0 + nr) of tile row block I into LDS: 4 doubles per row, the
-// point (zero past d and in the padding) and 1.0 / 0.0 for inside / padding
+// row points of rows [r0, r0 + nr) of tile row block I into LDS: 3 doubles per row, the point
+// (zero past d and in the padding), and behind the B rows' points bit r of the row mask: inside
+// / padding.  r0 and nr are multiples of 32 (a unit is at least a 16th of a tile), so a wave's
+// rows fill whole mask words: 64 rows two of them, the 32 rows of a 16th one.
+__device__ __forceinline__ bool gen_row_inside(const double *xrow, int r) {
+  const unsigned *mask = reinterpret_cast<const unsigned *>(xrow + kSymGenMaxD * B);
+  return ((mask[r >> 5] >> (r & 31)) & 1u) != 0u;
+}
 __device__ __forceinline__ void gen_stage_rows(const SymGen &gs, int I, int r0, int nr,
                                                double *__restrict__ xrow) {
+  unsigned *mask = reinterpret_cast<unsigned *>(xrow + kSymGenMaxD * B);
   for (int i = threadIdx.x; i < nr; i += 256) {
     int64_t g;
     const bool ok = gen_index(gs, (int64_t)I * B + r0 + i, g);
 #pragma unroll
     for (int t = 0; t < kSymGenMaxD; ++t)
-      xrow[4 * (r0 + i) + t] = (ok && t < gs.d) ? gs.Xs[g * gs.d + t] : 0.0;
-    xrow[4 * (r0 + i) + 3] = ok ? 1.0 : 0.0;
+      xrow[kSymGenMaxD * (r0 + i) + t] = (ok && t < gs.d) ? gs.Xs[g * gs.d + t] : 0.0;
+    const unsigned long long m = __ballot(ok);
+    if ((threadIdx.x & 63) == 0) {
+      mask[(r0 + i) >> 5] = (unsigned)m;
+      if (nr - i > 32) mask[((r0 + i) >> 5) + 1] = (unsigned)(m >> 32);
+    }
   }
 }
 // every position of block Jb inside [0, N) (positions are valid up to a first padded one)
@@ -217,11 +232,14 @@ __device__ __forceinline__ bool gen_block_full(const SymGen &gs, int Jb) {
   return p0 / gs.blk == p1 / gs.blk && gen_index(gs, p0, g) && gen_index(gs, p1, g);
 }
 // row r (tile-local) of a generated tile: the 8 entries of the lane's columns, the bits
-// k_sym_gen_rbf stores.  plain: an off-diagonal tile without padding (no selects)
+// k_sym_gen_rbf stores (rbf_of_sqdist_lean: exp's bits, common.h).  PLAIN: an off-diagonal tile
+// without padding, which nearly every tile is -- no select and no compare in the row
+template <bool PLAIN, bool DIAG>
 __device__ __forceinline__ void gen_row(const SymGen &gs, const GenCols &gc,
-                                        const double *__restrict__ xrow, int r, int lane, bool plain,
-                                        bool diag, d2 (&ar)[4]) {
-  const double *xr = xrow + 4 * r;
+                                        const double *__restrict__ xrow, int r, int lane,
+                                        d2 (&ar)[4]) {
+  static_assert(!(PLAIN && DIAG), "a diagonal tile is not plain");
+  const double *xr = xrow + kSymGenMaxD * r;
   double x[kSymGenMaxD];
 #pragma unroll
   for (int t = 0; t < kSymGenMaxD; ++t) x[t] = xr[t];
@@ -231,14 +249,14 @@ __device__ __forceinline__ void gen_row(const SymGen &gs, const GenCols &gc,
     double s = 0.0;
 #pragma unroll
     for (int t = 0; t < kSymGenMaxD; ++t) s = rbf_sqdist_step(s, __dsub_rn(gc.x[j][t], x[t]), t == 0);
-    v[j] = rbf_of_sqdist(s);
+    v[j] = rbf_of_sqdist_lean(s);
   }
-  if (!plain) {
-    const bool rv = xr[3] != 0.0;
+  if constexpr (!PLAIN) {
+    const bool rv = gen_row_inside(xrow, r);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const int c = 2 * (lane + 64 * (j >> 1)) + (j & 1);
-      if (diag && c == r) v[j] = 1.0 + gs.jitter;
+      if (DIAG && c == r) v[j] = 1.0 + gs.jitter;
       if (!(rv && ((gc.valid >> j) & 1u))) v[j] = 0.0;
     }
   }
@@ -249,12 +267,15 @@ __device__ __forceinline__ void gen_row(const SymGen &gs, const GenCols &gc,
 // ---- the tile body: what both schedules (k_symv_tiles, k_symv_dyn) and both roles do with a
 // unit, written once so that they all store the same bits ----
 
-// 8 rows [rbase, rbase + kRB) of the stored tile A, the lane's 4 double2 columns of each
+// RB rows [rbase, rbase + RB) of the stored tile A, the lane's 4 double2 columns of each.  RB:
+// the rows a wave holds in registers at once, 8 (a whole batch) or 4 (a half batch: 64 VGPRs
+// less, the third workgroup of a CU, k_symv_dyn)
+template <int RB>
 __device__ __forceinline__ void tile_load_batch(const double *A, int64_t rbase, int lane,
-                                                d2 (&a)[kRB][4]) {
+                                                d2 (&a)[RB][4]) {
   const d2 *rowp = reinterpret_cast<const d2 *>(A + rbase * B) + lane;
 #pragma unroll
-  for (int rr = 0; rr < kRB; ++rr)
+  for (int rr = 0; rr < RB; ++rr)
 #pragma unroll
     for (int q = 0; q < 4; ++q) a[rr][q] = __builtin_nontemporal_load(rowp + rr * (B / 2) + 64 * q);
 }
@@ -263,21 +284,31 @@ __device__ __forceinline__ void tile_load_batch(const double *A, int64_t rbase, 
 // lanes into rows[] (wave-private LDS transpose: lane 8 r + c adds lanes 8c .. 8c + 7 of row
 // r, then xor over c), the lane's column partials into acc (off the diagonal).  GEN: the
 // entries are evaluated from the points row by row instead of taken from the loaded batch a.
-template <bool GEN>
-__device__ __forceinline__ void tile_batch(const d2 (&a)[GEN ? 1 : kRB][4], const SymGen &gs,
+// The tile's kind is uniform over a unit.  The generating role is instantiated per kind (PLAIN,
+// DIAG: gen_row); the streaming role keeps `diag` as a run-time value -- one copy of its 8-row
+// batch loop per kind would cost it 140 VGPRs, i.e. the second workgroup of the CU.
+// RB (streaming): the rows held at once.  RB = 4 takes the batch as two half batches, the
+// second loaded (from A) when the first has been used; each row's s0 / s1 chain, its place in
+// the transpose and the row order of acc are those of RB = 8, so the sums are the same bits.
+template <bool GEN, bool PLAIN, bool DIAG, int RB>
+__device__ __forceinline__ void tile_batch(d2 (&a)[GEN ? 1 : RB][4], const double *A,
+                                           const SymGen &gs,
                                            const GenCols &gc, const double *xrow,
-                                           bool plain, bool diag, const d2 (&pc)[4],
+                                           bool diag_rt, const d2 (&pc)[4],
                                            const double *vrow, int rbase, int lane,
                                            double *red, double *rows,
                                            d2 (&acc)[4]) {
+  const bool diag = GEN ? DIAG : diag_rt;
 #pragma unroll(GEN ? 2 : kRB)
   for (int rr = 0; rr < kRB; ++rr) {
     d2 ar[4];
     if constexpr (GEN) {
-      gen_row(gs, gc, xrow, rbase + rr, lane, plain, diag, ar);
+      gen_row<PLAIN, DIAG>(gs, gc, xrow, rbase + rr, lane, ar);
     } else {
+      if constexpr (RB < kRB)
+        if (rr == RB) tile_load_batch<RB>(A, rbase + RB, lane, a);
 #pragma unroll
-      for (int q = 0; q < 4; ++q) ar[q] = a[rr][q];
+      for (int q = 0; q < 4; ++q) ar[q] = a[rr % RB][q];
     }
     double s0 = ar[0].x * pc[0].x;
     double s1 = ar[0].y * pc[0].y;
@@ -309,6 +340,36 @@ __device__ __forceinline__ void tile_batch(const d2 (&a)[GEN ? 1 : kRB][4], cons
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The wave's batches gb0 + w, gb0 + w + 4, ... of a unit (the first one's entries are already
+// loaded when streaming), and the one uniform branch per unit that picks the generated tile's kind
+template <bool GEN, bool PLAIN, bool DIAG, int RB>
+__device__ __forceinline__ void tile_batches(d2 (&a)[GEN ? 1 : RB][4], const double *A,
+                                             const SymGen &gs, const GenCols &gc, const double *xrow,
+                                             bool diag_rt, const d2 (&pc)[4], const double *vrow,
+                                             int gb0, int gb1, int w, int lane, double *red,
+                                             double *rows, d2 (&acc)[4]) {
+#pragma unroll 1
+  for (int g = gb0 + w; g < gb1; g += 4) {
+    if constexpr (!GEN)
+      if (g != gb0 + w) tile_load_batch<RB>(A, g * kRB, lane, a);
+    tile_batch<GEN, PLAIN, DIAG, RB>(a, A, gs, gc, xrow, diag_rt, pc, vrow, g * kRB, lane, red, rows,
+                                     acc);
+  }
+}
+template <bool GEN, int RB>
+__device__ __forceinline__ void tile_unit(d2 (&a)[GEN ? 1 : RB][4], const double *A,
+                                          const SymGen &gs, const GenCols &gc, const double *xrow,
+                                          bool plain, bool diag, const d2 (&pc)[4],
+                                          const double *vrow, int gb0, int gb1, int w, int lane,
+                                          double *red, double *rows, d2 (&acc)[4]) {
+  if (GEN && plain)
+    tile_batches<GEN, GEN, false, RB>(a, A, gs, gc, xrow, diag, pc, vrow, gb0, gb1, w, lane, red, rows, acc);
+  else if (GEN && diag)
+    tile_batches<GEN, false, GEN, RB>(a, A, gs, gc, xrow, diag, pc, vrow, gb0, gb1, w, lane, red, rows, acc);
+  else
+    tile_batches<GEN, false, false, RB>(a, A, gs, gc, xrow, diag, pc, vrow, gb0, gb1, w, lane, red, rows, acc);
 }
 
 // The wave's column partials of a unit into LDS for the 4-wave combine of tile_store_slots
@@ -356,7 +417,7 @@ __global__ __launch_bounds__(256) void k_symv_tiles(const double *__restrict__ t
 #pragma unroll
   for (int q = 0; q < 4; ++q)
     pc[q] = *reinterpret_cast<const d2 *>(v + (int64_t)t.y * B + 2 * (lane + 64 * q));
-  tile_load_batch(A, (int64_t)(gb0 + w) * kRB, lane, a);
+  tile_load_batch<kRB>(A, (int64_t)(gb0 + w) * kRB, lane, a);
   for (int i = gb0 * kRB + threadIdx.x; i < gb1 * kRB; i += 256) sh[i] = v[(int64_t)t.x * B + i];
   __syncthreads();
   const bool diag = t.x == t.y;
@@ -364,12 +425,8 @@ __global__ __launch_bounds__(256) void k_symv_tiles(const double *__restrict__ t
   d2 acc[4];
 #pragma unroll
   for (int q = 0; q < 4; ++q) acc[q] = d2{0.0, 0.0};
-#pragma unroll 1
-  for (int g = gb0 + w; g < gb1; g += 4) {
-    if (g != gb0 + w) tile_load_batch(A, g * kRB, lane, a);
-    tile_batch<false>(a, SymGen{}, none, nullptr, false, diag, pc, sh, g * kRB, lane,
-                      sh + kTileRed + w * kRB * 64, sh + B, acc);
-  }
+  tile_unit<false, kRB>(a, A, SymGen{}, none, nullptr, false, diag, pc, sh, gb0, gb1, w, lane,
+                   sh + kTileRed + w * kRB * 64, sh + B, acc);
   if (!diag) tile_stage_cols(acc, sh + 2 * B, w, lane);
   __syncthreads();
   tile_store_slots(P, Pq, Np, nb, t, h, gb0, gb1, diag, sh);
@@ -399,7 +456,7 @@ struct SymvArgs {
 // in where a unit's entries come from (GEN: the points, else the stream 8 rows ahead).
 // (The operand reads -- pc before a unit, vrow after the previous one's stores -- stay spelled
 // out at their two places each: as helpers they are scheduled differently, 2 VGPRs more.)
-template <bool GEN>
+template <bool GEN, int RB>
 __device__ __forceinline__ long long symv_units(const SymvArgs &k, const SymGen &gs, long long u,
                                                 UnitQueue q, double *__restrict__ sh,
                                                 long long *s_next) {
@@ -415,11 +472,11 @@ __device__ __forceinline__ long long symv_units(const SymvArgs &k, const SymGen 
   decode_unit(u, k.nwhole, k.lsub, tile, h, gb0, gb1);
   int2 t = k.list[tile];
   const double *A = k.tiles + (int64_t)tile * B * B;
-  d2 pc[4], a[GEN ? 1 : kRB][4];
+  d2 pc[4], a[GEN ? 1 : RB][4];
   GenCols gc;
 #pragma unroll
   for (int q = 0; q < 4; ++q) pc[q] = pg_val2(pg, v, (int64_t)t.y * B + 2 * (lane + 64 * q), beta);
-  if constexpr (!GEN) tile_load_batch(A, (int64_t)(gb0 + w) * kRB, lane, a);
+  if constexpr (!GEN) tile_load_batch<RB>(A, (int64_t)(gb0 + w) * kRB, lane, a);
   if (threadIdx.x == 0) *s_next = next_unit(q, k.nunits);
   for (int i = threadIdx.x; i < (gb1 - gb0) * kRB; i += 256) {
     const int64_t gi = (int64_t)t.x * B + gb0 * kRB + i;
@@ -436,12 +493,7 @@ __device__ __forceinline__ long long symv_units(const SymvArgs &k, const SymGen 
     d2 acc[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) acc[q] = d2{0.0, 0.0};
-#pragma unroll 1
-    for (int g = gb0 + w; g < gb1; g += 4) {
-      if constexpr (!GEN)
-        if (g != gb0 + w) tile_load_batch(A, g * kRB, lane, a);
-      tile_batch<GEN>(a, gs, gc, xrow, plain, diag, pc, vrow, g * kRB, lane, red, rows, acc);
-    }
+    tile_unit<GEN, RB>(a, A, gs, gc, xrow, plain, diag, pc, vrow, gb0, gb1, w, lane, red, rows, acc);
     if (!diag) tile_stage_cols(acc, cs, w, lane);
     __syncthreads();  // rows / cs complete; s_next visible
     const long long un = *s_next;
@@ -458,7 +510,7 @@ __device__ __forceinline__ long long symv_units(const SymvArgs &k, const SymGen 
       if constexpr (GEN)
         gen_load_cols(gs, t2.y, lane, gc);
       else
-        tile_load_batch(A2, (int64_t)(gb02 + w) * kRB, lane, a);
+        tile_load_batch<RB>(A2, (int64_t)(gb02 + w) * kRB, lane, a);
     }
     tile_store_slots(k.P, k.Pq, k.Np, k.nb, t, h, gb0, gb1, diag, sh);
     __syncthreads();  // LDS consumed, s_next read by everyone
@@ -503,8 +555,11 @@ constexpr int kTraceWords = 4;
 // another; it is therefore not known at launch how many workgroups hold a role, and every unit,
 // the first included, comes from a counter.  A workgroup done with its role's ranges goes on
 // with the other role's, in its own manner (the bits are the same, tile_batch<GEN>).
-template <bool ROLES>
-__global__ __launch_bounds__(256) void k_symv_dyn(const double *__restrict__ tiles,
+// RB: the rows the streaming role holds at once (tile_load_batch).  8: 220 VGPRs, two workgroups
+// on a CU, one of each role.  4 (ROLES only): at most 168 VGPRs and a third of the CU's LDS,
+// three workgroups on a CU, one streaming and two generating (gs.wgs).
+template <bool ROLES, int RB = kRB>
+__global__ __launch_bounds__(256, RB < kRB ? 3 : 1) void k_symv_dyn(const double *__restrict__ tiles,
                                                   const int2 *__restrict__ list,
                                                   const double *__restrict__ v,
                                                   double *__restrict__ P,
@@ -519,14 +574,18 @@ __global__ __launch_bounds__(256) void k_symv_dyn(const double *__restrict__ til
   // MLFF_SYM_TRACE (diagnostic): per workgroup its start, end, units taken, role and CU
   unsigned long long *tr = wgtrace != nullptr ? wgtrace + kTraceWords * blockIdx.x : nullptr;
   if (tr != nullptr && threadIdx.x == 0) tr[0] = wall_clock64();
-  __shared__ double sh[kTileLds + (ROLES ? 4 * B : 0)];
+  __shared__ double sh[kTileLds + (ROLES ? kGenRowLds : 0)];
   __shared__ long long s_next;
   __shared__ int s_role;
   if (!ROLES && (long long)blockIdx.x >= nunits) return;
   if (ROLES && threadIdx.x == 0) {
     int r = gs.roles == kSymRolesGen ? 1 : 0;
-    if (gs.roles == kSymRolesIndex) r = (int)(blockIdx.x & 1u);
-    if (gs.roles == kSymRolesCu) r = (int)(atomicAdd(ticket + kTicketWords + cu_key(), 1ull) & 1ull);
+    // of every gs.wgs workgroups (by index, or as they arrive on the CU) the first one streams.
+    // The arrival words are never reset, and a launch that ended early leaves them out of
+    // phase: that moves roles between workgroups, never a result
+    const unsigned wgs = (unsigned)gs.wgs;
+    if (gs.roles == kSymRolesIndex) r = blockIdx.x % wgs != 0u;
+    if (gs.roles == kSymRolesCu) r = atomicAdd(ticket + kTicketWords + cu_key(), 1ull) % wgs != 0ull;
     s_role = r;
   }
   if (!ROLES && tr != nullptr && threadIdx.x == 0) tr[3] = 1ull | (unsigned long long)cu_key() << 2;
@@ -569,11 +628,11 @@ __global__ __launch_bounds__(256) void k_symv_dyn(const double *__restrict__ til
   long long units_done;
   if constexpr (ROLES) {
     if (gen)
-      units_done = symv_units<true>(k, gs, u, q, sh, &s_next);
+      units_done = symv_units<true, RB>(k, gs, u, q, sh, &s_next);
     else
-      units_done = symv_units<false>(k, gs, u, q, sh, &s_next);
+      units_done = symv_units<false, RB>(k, gs, u, q, sh, &s_next);
   } else {
-    units_done = symv_units<false>(k, gs, u, q, sh, &s_next);
+    units_done = symv_units<false, RB>(k, gs, u, q, sh, &s_next);
   }
   if (tr != nullptr && threadIdx.x == 0) {
     tr[1] = wall_clock64();
@@ -1088,7 +1147,24 @@ __global__ __launch_bounds__(256) void k_sym_gen_rbf(const int2 *__restrict__ li
   }
 }
 
+// test hook (mlff_test_rbf_exp): both forms of the entry's exp over an array of squared distances
+__global__ __launch_bounds__(256) void k_rbf_exp_probe(const double *__restrict__ s, int64_t n,
+                                                       double *__restrict__ lib_out,
+                                                       double *__restrict__ lean_out) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+    lib_out[i] = rbf_of_sqdist(s[i]);
+    lean_out[i] = rbf_of_sqdist_lean(s[i]);
+  }
+}
+
 }  // namespace
+
+void launch_rbf_exp_probe(const double *s, int64_t n, double *lib_out, double *lean_out,
+                          hipStream_t st) {
+  if (n <= 0) return;
+  const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_rbf_exp_probe, dim3(grid), dim3(256), 0, st, s, n, lib_out, lean_out);
+}
 
 // The MLFF_SYM_* environment knobs (all A/B or diagnostic; the defaults are the measured
 // choices).  Read at every operator build, so a process may change them between contexts.
@@ -1127,6 +1203,11 @@ struct SymKnobs {
   // range is exhausted takes first, the other role's whole tiles or the quarter units.
   int roles = kSymRolesCu;
   int pool_first = 0;
+  // MLFF_SYM_WGS=2|3: the form of k_symv_dyn<true>, two resident workgroups per CU (8-row
+  // streaming batches, one workgroup of each role) or three (4-row half batches, one streaming
+  // and two generating); 0, the default: three where the operator has kSymThreeWgMinUnits
+  // units per workgroup, else two (sym_plan)
+  int wgs = 0;
   // MLFF_SYM_REDUCE_LIST=0: k_sym_reduce_w instead of k_sym_reduce_wl (W > 1)
   bool reduce_list = true;
   // MLFF_SYM_PQ_ORDERED=1: k_sym_reduce_wl's arrival in the formally ordered form (pq_put)
@@ -1157,6 +1238,10 @@ static SymKnobs sym_knobs() {
     if (std::strcmp(e, "gen") == 0) k.roles = kSymRolesGen;
   }
   if (const char *e = std::getenv("MLFF_SYM_STEAL")) k.pool_first = std::strcmp(e, "pool") == 0;
+  if (const char *e = std::getenv("MLFF_SYM_WGS")) {
+    const int v = std::atoi(e);
+    if (v == 2 || v == 3) k.wgs = v;
+  }
   if (const char *e = std::getenv("MLFF_SYM_REDUCE_LIST")) k.reduce_list = std::atoi(e) != 0;
   if (const char *e = std::getenv("MLFF_SYM_PQ_ORDERED")) k.pq_ordered = std::atoi(e) != 0;
   if (const char *e = std::getenv("MLFF_SYM_TRACE")) k.trace_at = std::atoll(e);
@@ -1166,7 +1251,8 @@ static SymKnobs sym_knobs() {
 // MLFF_SYM_TRACE: the ramp until every workgroup runs, the tail after the median one is done
 // (tr: start, end (10-ns ticks), units, role and CU of each of the G workgroups; one sync), and
 // where the dispatcher put the two roles
-static void print_symv_trace(const unsigned long long *tr, unsigned G, int64_t units, hipStream_t s) {
+static void print_symv_trace(const unsigned long long *tr, unsigned G, int64_t units, int wgs,
+                             hipStream_t s) {
   std::vector<unsigned long long> h((size_t)kTraceWords * G);
   if (hipStreamSynchronize(s) != hipSuccess ||
       hipMemcpy(h.data(), tr, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost) != hipSuccess)
@@ -1215,11 +1301,11 @@ static void print_symv_trace(const unsigned long long *tr, unsigned G, int64_t u
   for (int k = 0; k < kSymCuWords; ++k) {
     if (cu_s[k] + cu_g[k] == 0) continue;
     ++cus;
-    if (cu_s[k] == 1 && cu_g[k] == 1)
+    if (cu_s[k] == 1 && cu_g[k] == wgs - 1)
       ++paired;
-    else if (cu_s[k] == 2 && cu_g[k] == 0)
+    else if (cu_s[k] == wgs && cu_g[k] == 0)
       ++two_s;
-    else if (cu_s[k] == 0 && cu_g[k] == 2)
+    else if (cu_s[k] == 0 && cu_g[k] == wgs)
       ++two_g;
     else
       ++other;
@@ -1229,9 +1315,11 @@ static void print_symv_trace(const unsigned long long *tr, unsigned G, int64_t u
     if (xs[x] + xg[x] > 0)
       per_xcc += " " + std::to_string(x) + ":" + std::to_string(xs[x]) + "s+" + std::to_string(xg[x]) + "g";
   std::fprintf(stderr,
-               "[sym trace] roles: %d distinct CU keys; CUs holding {stream + gen} %d, {2 stream} %d, "
-               "{2 gen} %d, other %d; units taken stream / gen %.0f / %.0f; per XCC id%s\n",
-               cus, paired, two_s, two_g, other, un_s, un_g, per_xcc.c_str());
+               "[sym trace] roles: %d distinct CU keys; CUs holding {1 stream + %d gen} %d, {%d stream} "
+               "%d, {%d gen} %d, other %d; units taken stream / gen %.0f / %.0f (%.0f / %.0f per ms "
+               "of the span); per XCC id%s\n",
+               cus, wgs - 1, paired, wgs, two_s, wgs, two_g, other, un_s, un_g, 1e6 * un_s / span,
+               1e6 * un_g / span, per_xcc.c_str());
 }
 
 void launch_symv(const SymPack &sp, const double *v_full, double *P, const int *status,
@@ -1250,7 +1338,11 @@ void launch_symv(const SymPack &sp, const double *v_full, double *P, const int *
   if (trace_at > 0 && ++launches == trace_at &&
       hipMalloc(&tr, sizeof(unsigned long long) * kTraceWords * G) == hipSuccess)
     (void)hipMemsetAsync(tr, 0, sizeof(unsigned long long) * kTraceWords * G, s);
-  if (sp.gen)
+  if (sp.gen && sp.rb4)
+    hipLaunchKernelGGL((k_symv_dyn<true, 4>), dim3(G), dim3(256), 0, s,
+                       sp.tiles, sp.list, v_full, P, sp.Pq, sp.Np, (int)sp.nwhole, (long long)grid,
+                       (int)sp.nb, sp.lsub, sp.ticket, status, pg, sp.gsrc, tr);
+  else if (sp.gen)
     hipLaunchKernelGGL(k_symv_dyn<true>, dim3(G), dim3(256), 0, s,
                        sp.tiles, sp.list, v_full, P, sp.Pq, sp.Np, (int)sp.nwhole, (long long)grid,
                        (int)sp.nb, sp.lsub, sp.ticket, status, pg, sp.gsrc, tr);
@@ -1259,7 +1351,7 @@ void launch_symv(const SymPack &sp, const double *v_full, double *P, const int *
                        sp.tiles, sp.list, v_full, P, sp.Pq, sp.Np, (int)sp.nwhole, (long long)grid,
                        (int)sp.nb, sp.lsub, sp.ticket, status, pg, SymGen{}, tr);
   if (tr != nullptr) {
-    print_symv_trace(tr, G, grid, s);
+    print_symv_trace(tr, G, grid, sp.wgs, s);
     (void)hipFree(tr);
   }
 }
@@ -1356,6 +1448,8 @@ struct SymPlan {
   int lsub = 2;
   int64_t nq = 3;                   // Pq planes: 2^lsub - 1
   int64_t dyn = 0;                  // resident workgroups of k_symv_dyn, 0: k_symv_tiles
+  int wgs = 2;                      // ... per CU
+  bool rb4 = false;                 // k_symv_dyn<true, 4>, the three-workgroup form
   bool gen = false;
   SymGen gsrc;
 };
@@ -1402,8 +1496,28 @@ static SymPlan sym_plan(const mlff_ctx *ctx, const SymKnobs &kn) {
     if (n_s == pl.nwhole && qmode == 1) on = false;          // every unit streamed
     if (on) {
       pl.gen = true;
+      // the three-workgroup form: as many workgroups per CU as the runtime says are resident
+      // (registers and LDS of the 4-row instantiation: 3), and that many times the CUs in all.
+      // The unit set (nwhole, C) stays the two-workgroup form's, so the slots sum alike.
+      // It pays from kSymThreeWgMinUnits units per workgroup: with fewer, the launch ends on
+      // generating workgroups that took one more whole tile at their 0.15 ms each (two of them
+      // share a CU's SIMDs), as one rank of 8 at N = 65536 does -- 1056 units on 768
+      // workgroups, 0.349 against 0.300 ms per iteration -- while one rank of 4 (2112 units)
+      // gains 7 %, as one rank of 2 and the single GPU do (profiles/symlean/).
+      if (kn.wgs != 2) {
+        int occ = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_symv_dyn<true, 4>, 256, 0) != hipSuccess ||
+            occ < 1)
+          occ = 2;
+        const int64_t nunits = pl.nwhole + ((pl.nt - pl.nwhole) << pl.lsub);
+        pl.rb4 = kn.wgs == 3 || (occ > 2 && nunits >= kSymThreeWgMinUnits * occ * cus);
+        if (pl.rb4) {
+          pl.wgs = occ;
+          pl.dyn = (int64_t)occ * cus;
+        }
+      }
       pl.gsrc = SymGen{ctx->rbf.Xs, ctx->rbf.d, ctx->rbf.jitter, ctx->N, ctx->rows_per, ctx->blk,
-                       (int)n_s, qmode, kn.roles, kn.pool_first};
+                       (int)n_s, qmode, kn.roles, kn.pool_first, pl.wgs};
     }
   }
   return pl;
@@ -1449,6 +1563,8 @@ static int sym_alloc(mlff_ctx *ctx, const SymPlan &pl, const SymKnobs &kn) {
   sp.nwhole = pl.nwhole;
   sp.lsub = pl.lsub;
   sp.dyn = pl.dyn;
+  sp.wgs = pl.dyn > 0 ? pl.wgs : 0;
+  sp.rb4 = pl.rb4;
   sp.gen = pl.gen;
   sp.gsrc = pl.gsrc;
   sp.pq_ordered = kn.pq_ordered;

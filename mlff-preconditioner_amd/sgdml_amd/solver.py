@@ -231,6 +231,14 @@ class KernelSolver:
                                                                                 "dense")
         return name, nbytes.value
 
+    def sym_launch_info(self) -> tuple[int, int]:
+        """(resident workgroups per CU, workgroups in all) of the symmetric tile mat-vec's
+        persistent launch; (0, 0) under MLFF_SYM_SCHED=static."""
+        wgs = ctypes.c_int()
+        grid = ctypes.c_int64()
+        self._call("mlff_sym_launch_info", ctypes.byref(wgs), ctypes.byref(grid))
+        return wgs.value, grid.value
+
     def operator_form(self) -> str | None:
         """Form of the matrix-free sGDML operator: 'pair', 'rec' (record-factored, many atoms /
         few points) or 'pt' (pair-tile, few atoms / many points); None without one."""

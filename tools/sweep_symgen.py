@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Share sweep of the two-role tile mat-vec (k_symv_dyn<true>) on one GPU.
 
-    python tools/sweep_symgen.py [--n 65536] [--tiles 2048,2730,...] [--roles cu] --out FILE.json
+    python tools/sweep_symgen.py [--n 65536] [--tiles 2048,2730,...] [--roles cu] [--wgs 2|3]
+                                 --out FILE.json
 
 For each configuration a fresh operator is built from the same RBF points and timed over
 three runs of 10 unpreconditioned PCG steps (after 5 warm-up steps); x and the residual trace
@@ -30,15 +31,18 @@ import numpy as np
 REPO = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(REPO / "mlff-preconditioner_amd"))
 
-KEYS = ("MLFF_SYM_GEN", "MLFF_SYM_GEN_TILES", "MLFF_SYM_GEN_QUARTERS", "MLFF_SYM_ROLES")
+KEYS = ("MLFF_SYM_GEN", "MLFF_SYM_GEN_TILES", "MLFF_SYM_GEN_QUARTERS", "MLFF_SYM_ROLES",
+        "MLFF_SYM_WGS")
 
 
-def config_env(cfg: str, roles: str | None) -> dict:
+def config_env(cfg: str, roles: str | None, wgs: str | None = None) -> dict:
     if cfg == "off":
         return {"MLFF_SYM_GEN": "0"}
     cfg, _, forced = cfg.partition("/")
     t, q = cfg.split(":")
     env = {"MLFF_SYM_GEN_TILES": t, "MLFF_SYM_GEN_QUARTERS": q}
+    if wgs:
+        env["MLFF_SYM_WGS"] = wgs
     if forced or roles:
         env["MLFF_SYM_ROLES"] = forced or roles
     return env
@@ -84,6 +88,8 @@ def main() -> int:
     ap.add_argument("--whole", type=int, default=8192,
                     help="generated whole tiles of the all-generated configuration")
     ap.add_argument("--roles", default=None, help="MLFF_SYM_ROLES of the run (default: the library's)")
+    ap.add_argument("--wgs", choices=["2", "3"], default=None,
+                    help="MLFF_SYM_WGS of the run: workgroups per CU (default: the library's choice)")
     ap.add_argument("--pure", action="store_true", help="add the one-role configurations")
     ap.add_argument("--out", type=Path, required=True)
     a = ap.parse_args()
@@ -92,7 +98,7 @@ def main() -> int:
         cfgs += ["0:2/stream", f"{a.whole}:2/gen"]
     rows, first = [], None
     for cfg in cfgs:
-        env = config_env(cfg, a.roles)
+        env = config_env(cfg, a.roles, a.wgs)
         ms, nbytes, x, trace = run(env, a.n, a.lam, a.ell)
         if first is None:
             first = (x, trace)
