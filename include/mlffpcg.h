@@ -266,10 +266,16 @@ int mlff_sgdml_energies(mlff_ctx *ctx, const double *alphas, double *E_out, int6
  * independent of any operator or matrix of the context; replaces an earlier model.  The pair
  * stage runs in the tile form for D <= 288 and in the stream form otherwise;
  * MLFF_PRED_FORM=tile|stream (tile on a larger D: MLFF_ERR_ARG) and MLFF_PRED_SLAB=<queries
- * per pass> are read here.  No lattice, no cut-off, no alphas_E (use_E_cstr models). */
+ * per pass> are read here.  No lattice, no cut-off.  The model set here has no energy
+ * coefficients; those of a use_E_cstr model follow with mlff_predict_set_energy_coefficients. */
 int mlff_predict_set_model(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc_alpha,
                            int64_t M, int n_atoms, const int32_t *perms, int n_perms, double sig,
                            double std, double c);
+/* The energy coefficients alphas_E (M entries) of a model trained with use_E_cstr: GDMLPredict's
+ * alphas_E_lin (predict.py:364-368) and the K_fe / K_ee terms of its worker (predict.py:206-218).
+ * Called after mlff_predict_set_model, which clears them; NULL clears them too.  All zeros give
+ * the bits of the model without them.  MLFF_ERR_STATE before a model is set. */
+int mlff_predict_set_energy_coefficients(mlff_ctx *ctx, const double *alphas_E);
 /* GDMLPredict.predict(R) (predict.py:997-1110; worker _predict_wkr, :72-234; descriptors
  * Desc.from_R, desc.py:203-358; vec_dot_d_desc, desc.py:408-428): R (Q x n_atoms x 3) ->
  * E_out (Q) = std E + c, F_out (Q x 3 n_atoms) = std F.  Every query's result has the same bits
@@ -277,8 +283,9 @@ int mlff_predict_set_model(mlff_ctx *ctx, const double *R_desc, const double *R_
 int mlff_predict(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F_out);
 /* The prediction set up by mlff_predict_set_model: form_out 0 tile / 1 stream, slab_out the
  * queries per pass, and the algorithmic work of one query -- flops of the pair stage
- * (M n_perms (9 D + 10)) and bytes of the R_desc_perms / R_d_desc_alpha_perms stream
- * (predict.py:174-175).  No reference counterpart (measurement). */
+ * (M n_perms (9 D + 10); (9 D + 19) with energy coefficients) and bytes of the R_desc_perms /
+ * R_d_desc_alpha_perms (/ alphas_E_lin) stream (predict.py:174-175).  No reference counterpart
+ * (measurement). */
 int mlff_predict_info(mlff_ctx *ctx, int *form_out, int64_t *slab_out, double *flops_per_query_out,
                       double *bytes_per_query_out);
 

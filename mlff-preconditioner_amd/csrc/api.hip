@@ -1689,6 +1689,14 @@ int mlff_predict_set_model(mlff_ctx *ctx, const double *R_desc, const double *R_
   MLFF_API_END(ctx)
 }
 
+int mlff_predict_set_energy_coefficients(mlff_ctx *ctx, const double *alphas_E) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  if (!ctx->pred.ready) return set_error(ctx, MLFF_ERR_STATE, "predict: no model set (mlff_predict_set_model)");
+  return pred_set_energy_coefficients(ctx, alphas_E);
+  MLFF_API_END(ctx)
+}
+
 int mlff_predict(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F_out) {
   MLFF_API_BEGIN
   MLFF_ENTER(ctx);

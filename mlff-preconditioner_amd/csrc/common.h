@@ -204,7 +204,8 @@ struct PredData {
   int64_t slab = 0;        // queries per pass (bounds part)
   int64_t PS = 0, ecol = 0;  // row stride of part, column of the energy partial
   double *Rt = nullptr, *Zt = nullptr;      // MP x D
-  double *Rq = nullptr;                     // slab x n x 3 query geometries
+  double *Et = nullptr;                     // MP: alphas_E[j] per row (use_E_cstr models), else null
+  double *Rq = nullptr;                    // slab x n x 3 query geometries
   double *Rdq = nullptr, *Rddq = nullptr;   // slab x D, slab x D x 3
   double *part = nullptr;                   // S x slab x PS chunk partials
   double *Fd = nullptr;                     // slab x D
@@ -937,6 +938,9 @@ int desc_perm_tables(mlff_ctx *ctx, const int32_t *perms, int n, int n_perms,
 // are read here
 int pred_set_model(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc_alpha, int64_t M,
                    int n_atoms, const int32_t *perms, int n_perms, double sig, double std, double c);
+// the model's energy coefficients alphas_E (M entries; use_E_cstr models), null to clear them:
+// selects the constrained pair kernels
+int pred_set_energy_coefficients(mlff_ctx *ctx, const double *alphas_E);
 // E (Q), F (Q x 3 n) of the Q host geometries R, in slabs of pred.slab queries
 int pred_run(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F_out);
 bool pred_tile_supported(int64_t D);

@@ -13,6 +13,19 @@
 //   E = std E_q + c_int,  F = std F_q      (predict.py:1106-1108)
 // The pair arithmetic is k_pt_pair's (kernels_pt.hip) with one more fma per pair for the energy.
 //
+// Energy-constrained models (use_E_cstr: alphas_E, predict.py:206-218, alphas_E_lin at :364-368)
+// add, with e_jp = alphas_E[j] and x = nrm / sig,
+//   Fd_q += sum_jp e_jp w diff             (K_fe: the coefficient of diff becomes c + e_jp w)
+//   E_q  += sum_jp e_jp K_ee,  K_ee = (1 + x (1 + nrm / (3 sig))) exp(-x)
+// in the ECSTR instantiations of both pair stages (a template flag: the unconstrained ones are the
+// code they were).  The new terms enter as fma(e, w, c) and fma(e, K_ee, .) after the existing
+// ones, so alphas_E = 0 adds exact zeros and gives the unconstrained model's bits.  e_jp arrives
+// as an MP-long device array Et (alphas_E[j] repeated over p, the reference's alphas_E_lin): it
+// is 1 / (2 D) of the Rt / Zt rows it rides with, and the kernels need no division of a 64-bit
+// row index by n_perms.  The tile form stages it with the tile (rows past the chunk's end get 0,
+// as Rt / Zt do), the stream form reads it as one more per-row scalar (after the first pass: a
+// load ahead of the row stream cost a single query 4 %).
+//
 // Two forms of the pair stage, chosen by D (MLFF_PRED_FORM=tile|stream overrides):
 //  - tile (D <= 288), k_pr_pair<L, DL>: a workgroup of 128 threads holds G = 128 / L queries in
 //    registers, L lanes per query, DL entries per lane (interleaved pairs as in k_pt_pair), and
@@ -31,8 +44,9 @@
 // J_q^T Fd_q with the partners in increasing order (as k_pt_fin) and scales.
 //
 // Determinism: no atomics; the chunk count S, the tile shape and every reduction order depend on
-// the model (M n_perms, D, form) only, and no sum runs across queries: a query's E, F have the
-// same bits whatever the batch, its position in it, the slab size or the device split.
+// the model (M n_perms, D, form, constrained or not) only, and no sum runs across queries: a
+// query's E, F have the same bits whatever the batch, its position in it, the slab size or the
+// device split.
 #include "common.h"
 
 #include <algorithm>
@@ -63,6 +77,8 @@ struct PrArgs {
   double sig, sig2, inv_sig, k5;  // k5 = 5 / (3 sig^4)
   double *part;       // S x nq x PS
   int64_t PS, ecol;   // row stride of part and the column of the energy partial
+  const double *Et;   // MP energy coefficients alphas_E[j] (ECSTR kernels only)
+  double inv_3sig;    // 1 / (3 sig)
 };
 
 // Desc.from_R for the queries (k_desc's arithmetic, kernels_gen.hip) on the context's stream
@@ -97,8 +113,9 @@ __global__ __launch_bounds__(256) void k_pr_desc(const double *__restrict__ R, i
 constexpr int pr_tile_rows(int DP) { return DP <= 72 ? 16 : DP <= 144 ? 8 : 4; }
 
 // KEEP: diff and the Zt row stay in registers between the two passes over the lane's entries
-// (else they are formed / read from LDS again); WPE: waves per SIMD the registers are held to
-template <int L, int DL, bool KEEP, int WPE = 2>
+// (else they are formed / read from LDS again); WPE: waves per SIMD the registers are held to;
+// ECSTR: the model has energy coefficients (Et, staged with the tile)
+template <int L, int DL, bool KEEP, int WPE = 2, bool ECSTR = false>
 __global__ __launch_bounds__(kPrThreads) __attribute__((amdgpu_waves_per_eu(WPE, 8)))
 void k_pr_pair(PrArgs a) {
   static_assert(DL % 2 == 0 && 64 % L == 0, "lane layout");
@@ -110,6 +127,7 @@ void k_pr_pair(PrArgs a) {
   constexpr int KD = KEEP ? DL : 2;
   __shared__ double sR[kStage];
   __shared__ double sZ[kStage];
+  __shared__ double sE[ECSTR ? TJ : 1];
   const int tid = threadIdx.x;
   const int l = tid % L, g = tid / L;
   const int64_t q = (int64_t)blockIdx.x * G + g;
@@ -132,6 +150,7 @@ void k_pr_pair(PrArgs a) {
   const int64_t ntile = (jb1 - jb0 + TJ - 1) / TJ;
   // staging of tile t: rows jb0 + t TJ ..., entries past D and rows past jb1 zero
   double vr[kPer], vz[kPer];
+  double ve = 0.0;
   auto load_tile = [&](int64_t t) {
 #pragma unroll
     for (int u = 0; u < kPer; ++u) {
@@ -141,6 +160,10 @@ void k_pr_pair(PrArgs a) {
       const bool ok = e < kStage && jp < jb1 && d < a.D;
       vr[u] = ok ? a.Rt[jp * a.D + d] : 0.0;
       vz[u] = ok ? a.Zt[jp * a.D + d] : 0.0;
+    }
+    if (ECSTR) {
+      const int64_t jp = jb0 + t * TJ + tid;
+      ve = (tid < TJ && jp < jb1) ? a.Et[jp] : 0.0;
     }
   };
   if (ntile > 0) load_tile(0);
@@ -154,6 +177,7 @@ void k_pr_pair(PrArgs a) {
         sZ[e] = vz[u];
       }
     }
+    if (ECSTR && tid < TJ) sE[tid] = ve;
     __syncthreads();
     if (t + 1 < ntile) load_tile(t + 1);  // in flight during this tile's pairs
     const int64_t rem = jb1 - jb0 - t * TJ;
@@ -182,10 +206,17 @@ void k_pr_pair(PrArgs a) {
       }
       const double rs = group_sum<L>(r2a + r2b), as = group_sum<L>(aa + ab);
       const double nrm = kSqrt5 * sqrt(rs);
-      const double m = exp(-nrm * a.inv_sig) * a.k5;
+      const double ex = exp(-nrm * a.inv_sig);
+      const double m = ex * a.k5;
       const double w = fma(a.sig, nrm, a.sig2) * m;
-      const double c = 5.0 * m * as;
+      double c = 5.0 * m * as;
       en = fma(as, w, en);
+      if (ECSTR) {
+        const double ej = sE[j];
+        const double kee = fma(nrm * a.inv_sig, fma(nrm, a.inv_3sig, 1.0), 1.0) * ex;
+        c = fma(ej, w, c);
+        en = fma(ej, kee, en);
+      }
       // the second pass re-reads what it does not keep (no CSE of the LDS loads across this)
       if (!KEEP) asm volatile("" ::: "memory");
 #pragma unroll
@@ -222,7 +253,9 @@ void k_pr_pair(PrArgs a) {
 // 256, ...: a fixed order), summed over the workgroup wave by wave (shuffle tree) and the four
 // wave sums in wave order; then c, w per (query, row) and the entries of Fd, rows in increasing
 // order.  A thread owns the same entries in every step, so the chunk's partial accumulates in
-// part with plain loads and stores of its own entries (first step: stores only).
+// part with plain loads and stores of its own entries (first step: stores only).  ECSTR: the row's
+// energy coefficient joins c and the energy sum.
+template <bool ECSTR>
 __global__ __launch_bounds__(256) void k_pr_stream(PrArgs a) {
   constexpr int NV = 2 * kPrQB * kPrTB;
   __shared__ double sh[4][NV];
@@ -281,6 +314,10 @@ __global__ __launch_bounds__(256) void k_pr_stream(PrArgs a) {
     }
 #pragma unroll
     for (int v = 0; v < NV; ++v) acc[v] = wave_sum(acc[v]);
+    // the rows' energy coefficients: in flight across the two barriers
+    double ej[kPrTB];
+#pragma unroll
+    for (int t = 0; t < kPrTB; ++t) ej[t] = (ECSTR && rok[t]) ? a.Et[j0 + t] : 0.0;
     __syncthreads();  // sh of the previous step is consumed
     if (lane == 0) {
 #pragma unroll
@@ -296,11 +333,17 @@ __global__ __launch_bounds__(256) void k_pr_stream(PrArgs a) {
         const double rs = (sh[0][v] + sh[1][v]) + (sh[2][v] + sh[3][v]);
         const double as = (sh[0][v + 1] + sh[1][v + 1]) + (sh[2][v + 1] + sh[3][v + 1]);
         const double nrm = kSqrt5 * sqrt(rs);
-        const double m = exp(-nrm * a.inv_sig) * a.k5;
+        const double ex = exp(-nrm * a.inv_sig);
+        const double m = ex * a.k5;
         // a row past the chunk's end contributes nothing
         w[u][t] = rok[t] ? fma(a.sig, nrm, a.sig2) * m : 0.0;
         c[u][t] = rok[t] ? 5.0 * m * as : 0.0;
         if (rok[t]) en[u] = fma(as, w[u][t], en[u]);
+        if (ECSTR) {  // ej = 0 past the chunk's end (w = c = 0 there)
+          const double kee = fma(nrm * a.inv_sig, fma(nrm, a.inv_3sig, 1.0), 1.0) * ex;
+          c[u][t] = fma(ej[t], w[u][t], c[u][t]);
+          if (rok[t]) en[u] = fma(ej[t], kee, en[u]);
+        }
       }
     }
     const bool first = j0 == jb0;
@@ -418,17 +461,17 @@ using PrFn = void (*)(PrArgs);
 
 struct PrVariant {
   int L, DL;
-  PrFn fn;
+  PrFn fn, fn_e;  // without / with energy coefficients
 };
 
 // L lanes per query, DL entries per lane; the first variant that covers D is used (k_pt_pair's
 // shapes: DL = 18 fits the 36 entries of ethanol into two lanes)
 const PrVariant kPrVariants[] = {
-    {2, 18, k_pr_pair<2, 18, true>},   // D <= 36  (n <= 9)
-    {4, 18, k_pr_pair<4, 18, false>},  // D <= 72  (n <= 12)
-    {4, 28, k_pr_pair<4, 28, false>},  // D <= 112 (n <= 15)
-    {8, 28, k_pr_pair<8, 28, false>},  // D <= 224 (n <= 21)
-    {8, 36, k_pr_pair<8, 36, false, 1>},  // D <= 288 (n <= 24)
+    {2, 18, k_pr_pair<2, 18, true>, k_pr_pair<2, 18, true, 2, true>},      // D <= 36  (n <= 9)
+    {4, 18, k_pr_pair<4, 18, false>, k_pr_pair<4, 18, false, 2, true>},    // D <= 72  (n <= 12)
+    {4, 28, k_pr_pair<4, 28, false>, k_pr_pair<4, 28, false, 2, true>},    // D <= 112 (n <= 15)
+    {8, 28, k_pr_pair<8, 28, false>, k_pr_pair<8, 28, false, 2, true>},    // D <= 224 (n <= 21)
+    {8, 36, k_pr_pair<8, 36, false, 1>, k_pr_pair<8, 36, false, 1, true>}, // D <= 288 (n <= 24)
 };
 
 const PrVariant *pr_variant(int64_t D) {
@@ -449,7 +492,7 @@ int pr_alloc(mlff_ctx *ctx, T **p, int64_t count) {
 }  // namespace
 
 void pred_free(PredData &pd) {
-  for (double *p : {pd.Rt, pd.Zt, pd.Rq, pd.Rdq, pd.Rddq, pd.part, pd.Fd, pd.EF})
+  for (double *p : {pd.Rt, pd.Zt, pd.Et, pd.Rq, pd.Rdq, pd.Rddq, pd.part, pd.Fd, pd.EF})
     if (p != nullptr) (void)hipFree(p);
   for (double *p : {pd.h_in, pd.h_out})
     if (p != nullptr) (void)hipHostFree(p);
@@ -549,6 +592,27 @@ int pred_set_model(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc_a
   return MLFF_OK;
 }
 
+int pred_set_energy_coefficients(mlff_ctx *ctx, const double *alphas_E) {
+  PredData &pd = ctx->pred;
+  MLFF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  if (alphas_E == nullptr) {
+    if (pd.Et != nullptr) (void)hipFree(pd.Et);
+    pd.Et = nullptr;
+    return MLFF_OK;
+  }
+  // alphas_E_lin (predict.py:364-368): alphas_E[j] for every permuted copy jp = j n_perms + p
+  std::vector<double> hE((size_t)pd.MP);
+  for (int64_t j = 0; j < pd.M; ++j)
+    for (int p = 0; p < pd.n_perms; ++p) hE[(size_t)(j * pd.n_perms + p)] = alphas_E[j];
+  if (pd.Et == nullptr) MLFF_TRY(pr_alloc(ctx, &pd.Et, pd.MP));
+  if (hipMemcpy(pd.Et, hE.data(), sizeof(double) * pd.MP, hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(pd.Et);
+    pd.Et = nullptr;
+    return set_error(ctx, MLFF_ERR_HIP, "predict: upload of the energy coefficients failed");
+  }
+  return MLFF_OK;
+}
+
 int pred_run(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F_out) {
   const PredData &pd = ctx->pred;
   hipStream_t s = ctx->stream;
@@ -567,6 +631,9 @@ int pred_run(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F
   a.part = pd.part;
   a.PS = pd.PS;
   a.ecol = pd.ecol;
+  a.Et = pd.Et;
+  a.inv_3sig = 1.0 / (3.0 * pd.sig);
+  const bool ecstr = pd.Et != nullptr;
   for (int64_t q0 = 0; q0 < Q; q0 += pd.slab) {
     const int64_t nq = std::min<int64_t>(pd.slab, Q - q0);
     a.nq = nq;
@@ -577,11 +644,13 @@ int pred_run(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F
     hipLaunchKernelGGL(k_pr_desc, dim3(gx, (unsigned)nq), dim3(256), 0, s, pd.Rq, pd.n, pd.Rdq, pd.Rddq);
     if (pd.form == 0) {
       const PrVariant *v = pr_variant(D);
-      hipLaunchKernelGGL(v->fn, dim3((unsigned)((nq + pd.G - 1) / pd.G), (unsigned)pd.S),
-                         dim3(kPrThreads), 0, s, a);
+      hipLaunchKernelGGL(ecstr ? v->fn_e : v->fn,
+                         dim3((unsigned)((nq + pd.G - 1) / pd.G), (unsigned)pd.S), dim3(kPrThreads),
+                         0, s, a);
     } else {
-      hipLaunchKernelGGL(k_pr_stream, dim3((unsigned)((nq + kPrQB - 1) / kPrQB), (unsigned)pd.S),
-                         dim3(256), 0, s, a);
+      hipLaunchKernelGGL(ecstr ? k_pr_stream<true> : k_pr_stream<false>,
+                         dim3((unsigned)((nq + kPrQB - 1) / kPrQB), (unsigned)pd.S), dim3(256), 0, s,
+                         a);
     }
     hipLaunchKernelGGL(k_pr_sum, dim3((unsigned)((D + 1 + kPrSumE - 1) / kPrSumE), (unsigned)nq),
                        dim3(256), 0, s, pd.part, pd.PS, pd.ecol, D, nq, pd.S, pd.std, pd.c, pd.Fd, pd.EF);
@@ -598,10 +667,13 @@ int pred_run(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F
 }
 
 // algorithmic work of one query: 9 D + 10 flops per (j, p) pair (k_pt_pair's 9 D + 8 and the
-// energy fma), and the Rt / Zt rows every query block streams
+// energy fma), and the Rt / Zt rows every query block streams.  With energy coefficients 9 more
+// per pair: x = nrm / sig (1), K_ee = fma(x, fma(nrm, 1 / (3 sig), 1), 1) exp(-x) (2 + 2 + 1),
+// fma(e, w, c) (2) and fma(e, K_ee, en) (2); and the Et entry of every row.
 void pred_work(const PredData &pd, double *flops, double *bytes) {
-  *flops = (double)pd.MP * (9.0 * (double)pd.D + 10.0);
-  *bytes = 2.0 * 8.0 * (double)pd.MP * (double)pd.D;
+  const bool ecstr = pd.Et != nullptr;
+  *flops = (double)pd.MP * (9.0 * (double)pd.D + (ecstr ? 19.0 : 10.0));
+  *bytes = 8.0 * (double)pd.MP * (2.0 * (double)pd.D + (ecstr ? 1.0 : 0.0));
 }
 
 }  // namespace mlff

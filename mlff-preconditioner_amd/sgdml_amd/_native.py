@@ -74,6 +74,7 @@ SIGNATURES = {
     "mlff_test_rbf_exp": (_int, [_c_ctx, _p_dbl, _i64, _p_dbl, _p_dbl]),
     "mlff_predict_set_model": (_int, [_c_ctx, _p_dbl, _p_dbl, _i64, _int, _p_i32, _int, _dbl, _dbl,
                                       _dbl]),
+    "mlff_predict_set_energy_coefficients": (_int, [_c_ctx, _p_dbl]),
     "mlff_predict": (_int, [_c_ctx, _p_dbl, _i64, _p_dbl, _p_dbl]),
     "mlff_predict_info": (_int, [_c_ctx, _p_int, _p_i64, _p_dbl, _p_dbl]),
     "mlff_set_operator": (_int, [_c_ctx, _dbl, _dbl]),

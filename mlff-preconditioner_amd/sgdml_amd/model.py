@@ -18,9 +18,9 @@ model's energies and forces at held-out geometries, predicted on the GPU by
 can write into the model's `f_err` / `e_err` / `n_test` fields.
 
 Not covered: symmetry compression (`use_cprsn`), periodic lattices, the 'cg_cholesky' solver
-name, the closed-form solver's LU / least-squares fallbacks and more than one device for it,
-and prediction with energy-constrained models (`alphas_E`; GDMLPredict refuses them).  Energy
-constraints (`use_E_cstr`) train with 'analytic' only, as in the reference.
+name, the closed-form solver's LU / least-squares fallbacks and more than one device for it.
+Energy constraints (`use_E_cstr`) train with 'analytic' only, as in the reference; GDMLPredict
+and `test_errors` take the resulting models (`alphas_E`) like any other.
 """
 from __future__ import annotations
 

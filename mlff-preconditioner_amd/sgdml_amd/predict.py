@@ -1,12 +1,14 @@
 """GDMLPredict: energies and forces of a trained sGDML model at new geometries, on the MI355X.
 
 Drop-in for the reference's `sgdml.predict.GDMLPredict` (src/sGDML/sgdml/predict.py:237-384,
-997-1110) for models without lattice, cut-off or energy constraints:
+997-1110) for models without lattice or cut-off, with or without energy constraints (`alphas_E`
+of a model trained with `use_E_cstr`, predict.py:206-218):
 
     with GDMLPredict("model.npz") as gdml:      # or a model dict / an open np.load result
         E, F = gdml.predict(R)                  # R: Q x 3n, Q x n x 3, 3n or n x 3
 
-The model arrays go to the device once (`mlff_predict_set_model`); every `predict` call sends
+The model arrays go to the device once (`mlff_predict_set_model`,
+`mlff_predict_set_energy_coefficients`); every `predict` call sends
 the geometries and gets E (Q,) and F (Q, 3n) back (`mlff_predict`, csrc/kernels_predict.hip).
 A query's result has the same bits whatever batch it is part of, so splitting a batch over
 `devices=[...]` (contiguous blocks, one context and one thread per entry) changes nothing.
@@ -47,11 +49,13 @@ def _has(model, key):
     return key in files if files is not None else key in model
 
 
-def load_model_arrays(model) -> dict:
+def load_model_arrays(model, energy_constraints: bool = False) -> dict:
     """The arrays the predictor needs from a model dict, an open `np.load` result or the path
     of a `.npz` (written by `store_model` or by the reference): sig, std, c, R_desc (stored
     D x M, returned M x D), R_d_desc_alpha (M x D), perms (n_perms x n), z.  Scalars may be
-    0-d arrays.  Only these keys are read, so pickled entries of the file are never loaded."""
+    0-d arrays.  Only these keys are read, so pickled entries of the file are never loaded.
+    A model with `alphas_E` is refused unless `energy_constraints` is set; then the result also
+    has "alphas_E": a contiguous float64 (M,) array, or None for a model without the key."""
     opened = None
     if isinstance(model, (str, os.PathLike)):
         opened = model = np.load(model, allow_pickle=False)
@@ -62,7 +66,7 @@ def load_model_arrays(model) -> dict:
                 raise ValueError("the provided data structure is not a model (type != 'm')")
         if _has(model, "lattice"):
             raise NotImplementedError("models with a periodic lattice are not supported")
-        if _has(model, "alphas_E"):
+        if not energy_constraints and _has(model, "alphas_E"):
             raise NotImplementedError("models with energy constraints (alphas_E) are not supported")
         if _has(model, "interact_cut_off"):
             try:
@@ -91,7 +95,15 @@ def load_model_arrays(model) -> dict:
             raise ValueError(f"model['R_d_desc_alpha'] must be {M} x {D}, got {Rda.shape}")
         if not np.array_equal(np.sort(perms, axis=1), np.broadcast_to(np.arange(n), perms.shape)):
             raise ValueError("model['perms']: every row must be a permutation of the atoms")
-        return {
+        out = {}
+        if energy_constraints:
+            out["alphas_E"] = None
+            if _has(model, "alphas_E"):
+                aE = np.asarray(model["alphas_E"])
+                if aE.shape != (M,):
+                    raise ValueError(f"model['alphas_E'] must have shape ({M},), got {aE.shape}")
+                out["alphas_E"] = np.ascontiguousarray(aE, dtype=np.float64)
+        out.update({
             "sig": _scalar(model["sig"], "sig"),
             "std": _scalar(model["std"], "std") if _has(model, "std") else 1.0,
             "c": _scalar(model["c"], "c"),
@@ -99,7 +111,8 @@ def load_model_arrays(model) -> dict:
             "R_d_desc_alpha": np.ascontiguousarray(Rda),
             "perms": perms,
             "z": z.copy(),
-        }
+        })
+        return out
     finally:
         if opened is not None:
             opened.close()
@@ -130,11 +143,12 @@ def split_blocks(Q: int, parts: int) -> list[tuple[int, int]]:
 
 class GDMLPredict:
     def __init__(self, model, device: int | None = None, devices=None):
-        arrs = load_model_arrays(model)
+        arrs = load_model_arrays(model, energy_constraints=True)
         self.n_atoms = arrs["z"].size
         self.n_train = arrs["R_desc"].shape[0]
         self.n_perms = arrs["perms"].shape[0]
         self.sig, self.std, self.c = arrs["sig"], arrs["std"], arrs["c"]
+        self.use_E_cstr = arrs["alphas_E"] is not None
         self._lock = threading.Lock()
         self._workers = None
         self._engines: list[KernelSolver] = []
@@ -144,7 +158,7 @@ class GDMLPredict:
             s = KernelSolver(n_global, device=dev)
             try:
                 s.predict_set_model(arrs["R_desc"], arrs["R_d_desc_alpha"], arrs["perms"],
-                                    self.sig, self.std, self.c)
+                                    self.sig, self.std, self.c, alphas_E=arrs["alphas_E"])
             except BaseException:
                 s.close()
                 raise

@@ -171,10 +171,11 @@ class KernelSolver:
 
     # -------------------------------------------------------------- prediction
     def predict_set_model(self, R_desc: np.ndarray, R_d_desc_alpha: np.ndarray, perms: np.ndarray,
-                          sig: float, std: float = 1.0, c: float = 0.0):
+                          sig: float, std: float = 1.0, c: float = 0.0, alphas_E=None):
         """Hold a trained sGDML model for `predict` (GDMLPredict.__init__, predict.py:294-362):
-        R_desc and R_d_desc_alpha as M x D, perms n_perms x n_atoms.  The solver's N must be
-        3 n_atoms M; independent of any operator set on it."""
+        R_desc and R_d_desc_alpha as M x D, perms n_perms x n_atoms, alphas_E (M,) for a model
+        trained with energy constraints (None otherwise).  The solver's N must be 3 n_atoms M;
+        independent of any operator set on it.  A refused model leaves the earlier one in place."""
         R_desc = np.ascontiguousarray(R_desc, dtype=np.float64)
         Rda = np.ascontiguousarray(R_d_desc_alpha, dtype=np.float64)
         perms = np.ascontiguousarray(np.atleast_2d(perms), dtype=np.int32)
@@ -184,9 +185,26 @@ class KernelSolver:
         n_atoms = perms.shape[1]
         if Rda.shape != (M, D) or D != n_atoms * (n_atoms - 1) // 2:
             raise ValueError("R_desc / R_d_desc_alpha / perms shapes do not match")
+        if alphas_E is not None:
+            alphas_E = np.ascontiguousarray(alphas_E, dtype=np.float64)
+            if alphas_E.shape != (M,):
+                raise ValueError(f"alphas_E must have shape ({M},), got {alphas_E.shape}")
         self._call("mlff_predict_set_model", nat.dptr(R_desc), nat.dptr(Rda), int(M), int(n_atoms),
                    nat.i32ptr(perms), int(perms.shape[0]), float(sig), float(std), float(c))
         self._pred_n_atoms = n_atoms
+        self._pred_n_train = M
+        if alphas_E is not None:
+            self._call("mlff_predict_set_energy_coefficients", nat.dptr(alphas_E))
+
+    def predict_set_energy_coefficients(self, alphas_E):
+        """The energy coefficients alphas_E (M,) of the model set by `predict_set_model`
+        (GDMLPredict's alphas_E_lin, predict.py:364-368); None clears them."""
+        if alphas_E is not None:
+            alphas_E = np.ascontiguousarray(alphas_E, dtype=np.float64)
+            M = getattr(self, "_pred_n_train", None)
+            if M is not None and alphas_E.shape != (M,):
+                raise ValueError(f"alphas_E must have shape ({M},), got {alphas_E.shape}")
+        self._call("mlff_predict_set_energy_coefficients", nat.dptr(alphas_E))
 
     def predict(self, R: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
         """E (Q,), F (Q, 3 n_atoms) of the geometries R (Q x n_atoms x 3) with the model set by

@@ -2,6 +2,7 @@
 
     python tools/bench_predict.py [--legs ethanol nanotube ratio] [--reps 15] [--warmup 3]
                                   [--operator-lib /path/to/another/libmlffpcg.so]
+                                  [--energy-constraints]
 
 One JSON line per measurement:
   ethanol_like   M = 5833 (synthetic provides no symmetries: n_perms = 1), tile form,
@@ -14,6 +15,10 @@ One JSON line per measurement:
                  matrix-free pair-tile operator on the same geometries (the same pairs, minus the
                  energy fma); --operator-lib times the operator of another build of the library
                  (the parent commit's) in the same session
+--energy-constraints gives the models of the ethanol and nanotube legs random energy
+coefficients (alphas_E ~ N(0, 1), as a model trained with use_E_cstr carries), so that the
+constrained pair kernels are the ones timed; the records then say "use_E_cstr": true.  The ratio
+leg keeps the unconstrained model: the operator it is compared with has no energy rows.
 Every figure is the median of --reps calls after --warmup calls, each call bracketed by HIP
 events on the context's stream (the call's copies in and out included, for the prediction and
 for the mat-vec alike).
@@ -67,7 +72,7 @@ def median_ms(ev, stream, fn, reps, warmup):
     return float(np.median([ev.time_ms(stream, fn) for _ in range(reps)]))
 
 
-def build_model(ds, seed):
+def build_model(ds, seed, energy_constraints=False):
     from sgdml_amd.model import r_d_desc_alpha
     from sgdml_amd.solver import host_descriptors
 
@@ -76,6 +81,8 @@ def build_model(ds, seed):
     alphas = np.random.default_rng(seed).standard_normal(3 * n * M)
     model = {"type": "m", "z": ds["z"], "perms": np.arange(n)[None, :], "sig": 10.0, "std": 1.0,
              "c": 0.0, "R_desc": Rd.T, "R_d_desc_alpha": r_d_desc_alpha(Rdd, alphas)}
+    if energy_constraints:
+        model["alphas_E"] = np.random.default_rng(seed + 100).standard_normal(M)
     return model, Rd, Rdd, alphas
 
 
@@ -97,7 +104,8 @@ def predict_leg(name, ds, model, Qs, form, ev, reps, warmup):
         for Q in Qs:
             R = queries(ds, Q, 1000 + Q)
             ms = median_ms(ev, stream, lambda: eng.predict(R), reps, warmup)
-            rec = {"leg": name, "form": gd.form, "M": int(ds["R"].shape[0]), "Q": int(Q),
+            rec = {"leg": name, "form": gd.form, "use_E_cstr": bool(gd.use_E_cstr),
+                   "M": int(ds["R"].shape[0]), "Q": int(Q),
                    "slab": int(gd.slab), "us_per_call": ms * 1e3, "geometries_per_s": Q / (ms * 1e-3)}
             if form == "tile":
                 fl = gd.flops_per_query * Q / (ms * 1e-3)
@@ -164,6 +172,7 @@ def main():
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--operator-lib", default=None)
+    ap.add_argument("--energy-constraints", action="store_true")
     a = ap.parse_args()
     import sgdml_amd
     from sgdml_amd import _native, synthetic
@@ -175,7 +184,10 @@ def main():
         ds = synthetic.ethanol_like(5833, seed=0)
         model, Rd, Rdd, alphas = build_model(ds, 1)
         if "ethanol" in a.legs:
-            predict_leg("ethanol_like", ds, model, [1, 64, 4096], "tile", ev, a.reps, a.warmup)
+            leg_model = model
+            if a.energy_constraints:
+                leg_model = build_model(ds, 1, True)[0]
+            predict_leg("ethanol_like", ds, leg_model, [1, 64, 4096], "tile", ev, a.reps, a.warmup)
         if "ratio" in a.legs:
             M = ds["R"].shape[0]
             with sgdml_amd.GDMLPredict(model, device=0) as gd:
@@ -192,7 +204,7 @@ def main():
                 flush=True)
     if "nanotube" in a.legs:
         ds = synthetic.nanotube_like(141, seed=0)
-        model, _, _, _ = build_model(ds, 2)
+        model, _, _, _ = build_model(ds, 2, a.energy_constraints)
         predict_leg("nanotube_like", ds, model, [1, 16], "stream", ev, a.reps, a.warmup)
 
 
