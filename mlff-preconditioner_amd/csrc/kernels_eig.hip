@@ -16,7 +16,9 @@
 //         kernels_dense.hip; G all-reduced over the ranks, factored replicated)
 //   every 4 iterations Rayleigh-Ritz: H = Q (S Q)^T (b x b), H = V diag(theta) V^T by a
 //         cyclic parallel Jacobi on the device, Q <- V^T Q, stop when every one of the k
-//         leading Ritz pairs has ||S u - theta u|| <= 1e-11 |theta_0|.
+//         leading Ritz pairs has ||S u - theta u|| <= 1e-11 |theta_0|, and then once more
+//         (one polishing cycle).  theta are Rayleigh quotients of the re-orthonormalised
+//         Jacobi vectors (jacobi_eigh), not the rotated diagonal.
 //   When b >= N / 2 the subspace is the whole space (Q = I, one Rayleigh-Ritz = the full
 //   eigen-decomposition of S by Jacobi).
 //
@@ -176,6 +178,25 @@ __global__ void k_set_identity(double *__restrict__ V, int b) {
   V[e] = (e / b == e % b) ? 1.0 : 0.0;
 }
 
+// G <- 1.5 I - 0.5 G (b x b): the Newton-Schulz factor of G = V^T V
+__global__ void k_ns_factor(double *__restrict__ G, int b) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)b * b) return;
+  G[e] = ((e / b == e % b) ? 1.5 : 0.0) - 0.5 * G[e];
+}
+
+// rq[j] = sum_i V[i, j] W[i, j] (b x b, one workgroup per column)
+__global__ __launch_bounds__(256) void k_col_dots(const double *__restrict__ V,
+                                                  const double *__restrict__ W, int b,
+                                                  double *__restrict__ rq) {
+  __shared__ double sh[8];
+  const int j = blockIdx.x;
+  double a = 0.0;
+  for (int i = threadIdx.x; i < b; i += 256) a = fma(V[(int64_t)i * b + j], W[(int64_t)i * b + j], a);
+  a = block_sum256(a, sh);
+  if (threadIdx.x == 0) rq[j] = a;
+}
+
 // Vs[:, j] = V[:, ord[j]] (b x b)
 __global__ void k_permute_cols(const double *__restrict__ V, const int *__restrict__ ord, int b,
                                double *__restrict__ Vs) {
@@ -262,24 +283,45 @@ constexpr double kEigAcceptTol = 1e-6;
 constexpr int kEigMaxIter = 600;    // subspace iterations
 constexpr int kEigRREvery = 4;      // Rayleigh-Ritz every this many iterations
 constexpr int kJacMaxSweeps = 60;
+constexpr int kJacRefineMax = 4096;  // largest b whose eigenpairs are refined (three b x b scratch matrices)
 
 unsigned grid1(int64_t n) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 65535)); }
 
 }  // namespace
 
 // symmetric eigen-decomposition H = V diag(theta) V^T of a b x b matrix in device memory
-// (H is overwritten by diag(theta) to rounding, V by the eigenvectors as columns)
-int jacobi_eigh(mlff_ctx *ctx, double *H, int b, double *V) {
+// (H is overwritten by diag(theta) to rounding, V by the eigenvectors as columns).
+// rq (device, b entries, optional): the eigenvalues.  Every entry of H and V goes through
+// ~b rotations per sweep, so the rotated diagonal and V^T V - I carry some 30 to 100 roundings
+// (measured against a long-double decomposition: 1.4e-14 to 3e-14 of |theta_0| at b = 64 / 129,
+// LAPACK 1.4e-15).  For b <= kJacRefineMax, V is therefore re-orthonormalised by one
+// Newton-Schulz step, V <- V (1.5 I - 0.5 V^T V), and rq_j = v_j^T H v_j is the Rayleigh
+// quotient with the H that came in (second order in v_j's error); beyond that size rq is the
+// rotated diagonal.
+int jacobi_eigh(mlff_ctx *ctx, double *H, int b, double *V, double *rq = nullptr) {
   hipStream_t s = ctx->stream;
   ScratchScope scope(ctx);
   const int m = b + (b & 1);
   const int np = m / 2;
-  double *cs = nullptr, *part = nullptr;
+  const size_t bb = (size_t)b * b;
+  double *cs = nullptr, *part = nullptr, *H0 = nullptr, *W = nullptr, *M = nullptr;
   MLFF_TRY(scratch_alloc(ctx, &cs, 2 * (size_t)np));
   constexpr int kNormBlocks = 128;
   MLFF_TRY(scratch_alloc(ctx, &part, 2 * kNormBlocks));
+  const bool refine = rq != nullptr && b >= 2 && b <= kJacRefineMax;
+  if (refine) {
+    MLFF_TRY(scratch_alloc(ctx, &H0, bb));
+    MLFF_TRY(scratch_alloc(ctx, &W, bb));
+    MLFF_TRY(scratch_alloc(ctx, &M, bb));
+    MLFF_HIP(ctx, hipMemcpyAsync(H0, H, sizeof(double) * bb, hipMemcpyDeviceToDevice, s));
+  }
+  auto diag_to_rq = [&]() -> int {
+    MLFF_HIP(ctx, hipMemcpy2DAsync(rq, sizeof(double), H, sizeof(double) * (b + 1), sizeof(double),
+                                   b, hipMemcpyDeviceToDevice, s));
+    return MLFF_OK;
+  };
   hipLaunchKernelGGL(k_set_identity, dim3(grid1((int64_t)b * b)), dim3(256), 0, s, V, b);
-  if (b < 2) return MLFF_OK;
+  if (b < 2) return rq != nullptr ? diag_to_rq() : MLFF_OK;
   std::vector<double> h(2 * kNormBlocks);
   const dim3 gcols((unsigned)np, (unsigned)((b + 255) / 256));
   for (int sweep = 0; sweep < kJacMaxSweeps; ++sweep) {
@@ -298,6 +340,15 @@ int jacobi_eigh(mlff_ctx *ctx, double *H, int b, double *V) {
     }
     MLFF_HIP(ctx, hipGetLastError());
   }
+  if (rq == nullptr) return MLFF_OK;
+  if (!refine) return diag_to_rq();
+  launch_gemm(true, false, b, b, b, 1.0, V, b, V, b, 0.0, M, b, s);    // V^T V
+  hipLaunchKernelGGL(k_ns_factor, dim3(grid1((int64_t)bb)), dim3(256), 0, s, M, b);
+  launch_gemm(false, false, b, b, b, 1.0, V, b, M, b, 0.0, W, b, s);
+  MLFF_HIP(ctx, hipMemcpyAsync(V, W, sizeof(double) * bb, hipMemcpyDeviceToDevice, s));
+  launch_gemm(false, false, b, b, b, 1.0, H0, b, V, b, 0.0, W, b, s);  // H V
+  hipLaunchKernelGGL(k_col_dots, dim3((unsigned)b), dim3(256), 0, s, V, W, b, rq);
+  MLFF_HIP(ctx, hipGetLastError());
   return MLFF_OK;
 }
 
@@ -306,9 +357,23 @@ namespace {
 // W (b x ncols wide, row stride ldw) <- C^-1 W with C C^T = W W^T (+ shift): orthonormal
 // rows, nested spans.  Shifted CholeskyQR3 (Fukaya et al.): the first pass shifts the Gram
 // matrix by 11 (N b + b (b + 1)) u ||W||_F^2 so the Cholesky exists for any conditioning.
-int chol_qr3(mlff_ctx *ctx, double *W, int64_t b, int64_t ldw, double *G) {
+//
+// The two plain passes that follow a shifted one are what makes the result orthonormal (the
+// shifted pass only brings the condition number within reach of CholeskyQR2).  So when a plain
+// pass loses definiteness and is repeated shifted -- W = S Q exactly rank-deficient, a subspace
+// wider than rank S -- two plain passes follow that one too (at most kCholQrMaxPasses in all;
+// before, the third pass was the last whatever it was, and the rows of Q past the rank stayed
+// 1e-2 away from orthogonal to the rest: the Rayleigh-Ritz pairs of a three-atom sGDML operator
+// with b = 67 > rank 60 stalled at a residual of 1e-9 |theta_0| for all 600 iterations).
+// Without a retry the passes are the three they were.  *orthonormal_out: whether the two plain
+// passes were reached; a Q that missed them is still iterated on (its span is right), but its
+// Rayleigh-Ritz pairs are not accepted as converged (eig_lowrank, mlff_eig_info).
+constexpr int kCholQrMaxPasses = 8;
+
+int chol_qr3(mlff_ctx *ctx, double *W, int64_t b, int64_t ldw, double *G, bool *orthonormal_out) {
   hipStream_t s = ctx->stream;
-  for (int pass = 0; pass < 3; ++pass) {
+  int plain = 0;
+  for (int pass = 0; plain < 2 && pass < kCholQrMaxPasses; ++pass) {
     MLFF_TRY(syrk_wide(ctx, W, b, ctx->blk, ldw, G));
     MLFF_TRY(comm_allreduce(ctx, G, (size_t)(b * b)));
     bool shift = pass == 0;
@@ -329,6 +394,7 @@ int chol_qr3(mlff_ctx *ctx, double *W, int64_t b, int64_t ldw, double *G) {
       const int rc = potrf_lower(ctx, Gf, b);
       if (rc == MLFF_OK) {
         MLFF_TRY(trsm_lower_wide(ctx, Gf, b, W, ctx->blk, ldw));
+        plain = shift ? 0 : plain + 1;
         break;
       }
       if (rc != MLFF_ERR_LINALG || shift) return rc;
@@ -336,6 +402,7 @@ int chol_qr3(mlff_ctx *ctx, double *W, int64_t b, int64_t ldw, double *G) {
       shift = true;  // plain pass lost definiteness: repeat it shifted
     }
   }
+  *orthonormal_out = plain >= 2;
   return MLFF_OK;
 }
 
@@ -387,7 +454,7 @@ int eig_lowrank(mlff_ctx *ctx, int64_t k, int mask_mode, int64_t dim_i, double *
   const bool full = 2 * (k + std::max<int64_t>(16, k / 2)) >= n;
   const int64_t b = full ? n : std::min<int64_t>(n, k + std::max<int64_t>(16, k / 2));
   double *Q = nullptr, *Y = nullptr, *T = nullptr, *G = nullptr, *V = nullptr, *Vs = nullptr;
-  double *theta_d = nullptr, *res_d = nullptr;
+  double *theta_d = nullptr, *res_d = nullptr, *rq_d = nullptr;
   int *ord_d = nullptr;
   const size_t panel = (size_t)round_up(b, 8) * blk;
   MLFF_TRY(scratch_alloc(ctx, &Q, panel));
@@ -398,20 +465,26 @@ int eig_lowrank(mlff_ctx *ctx, int64_t k, int mask_mode, int64_t dim_i, double *
   MLFF_TRY(scratch_alloc(ctx, &Vs, (size_t)b * b));
   MLFF_TRY(scratch_alloc(ctx, &theta_d, b));
   MLFF_TRY(scratch_alloc(ctx, &res_d, b));
+  MLFF_TRY(scratch_alloc(ctx, &rq_d, b));
   MLFF_TRY(scratch_alloc(ctx, &ord_d, b));
   MLFF_HIP(ctx, hipMemsetAsync(Q, 0, sizeof(double) * panel, s));
   MLFF_HIP(ctx, hipMemsetAsync(Y, 0, sizeof(double) * panel, s));
+  bool q_orth = true;  // the Q in hand came out of chol_qr3 orthonormal (or is the identity)
   if (full) {
     hipLaunchKernelGGL(k_eig_identity, dim3(grid1(b)), dim3(256), 0, s, Q, blk, b, ctx->row0, nrows);
   } else {
     if (nrows > 0)
       hipLaunchKernelGGL(k_eig_rand, dim3((unsigned)std::min<int64_t>((nrows + 255) / 256, 64), (unsigned)b),
                          dim3(256), 0, s, Q, blk, nrows, ctx->row0, (uint64_t)0x5EEDull);
-    MLFF_TRY(chol_qr3(ctx, Q, b, blk, G));
+    MLFF_TRY(chol_qr3(ctx, Q, b, blk, G, &q_orth));
   }
   std::vector<double> theta(b), res(b);
   std::vector<int> ord(b);
   bool converged = false;
+  // the pairs that meet the tolerance get one more cycle before they are accepted: the residual
+  // falls by |lambda_{b+1} / lambda_k|^4 per cycle, so wherever the iteration converges at all
+  // the accepted subspace is then at rounding instead of somewhere below 1e-11
+  bool polished = false;
   for (int it = 1; it <= (full ? 1 : kEigMaxIter) && !converged; ++it) {
     for (int64_t j = 0; j < b; ++j) MLFF_TRY(apply(Q + j * blk, Y + j * blk));
     if (full || it % kEigRREvery == 0 || it == kEigMaxIter) {
@@ -419,10 +492,9 @@ int eig_lowrank(mlff_ctx *ctx, int64_t k, int mask_mode, int64_t dim_i, double *
       MLFF_TRY(gram_wide(ctx, Q, Y, b, blk, blk, G));
       MLFF_TRY(comm_allreduce(ctx, G, (size_t)(b * b)));
       hipLaunchKernelGGL(k_symmetrize, dim3(grid1(b * b)), dim3(256), 0, s, G, (int)b);
-      MLFF_TRY(jacobi_eigh(ctx, G, (int)b, V));
+      MLFF_TRY(jacobi_eigh(ctx, G, (int)b, V, rq_d));
       std::vector<double> hd(b);
-      MLFF_HIP(ctx, hipMemcpy2DAsync(hd.data(), sizeof(double), G, sizeof(double) * (b + 1),
-                                     sizeof(double), b, hipMemcpyDeviceToHost, s));
+      MLFF_HIP(ctx, hipMemcpyAsync(hd.data(), rq_d, sizeof(double) * b, hipMemcpyDeviceToHost, s));
       MLFF_HIP(ctx, hipStreamSynchronize(s));
       std::iota(ord.begin(), ord.end(), 0);
       std::stable_sort(ord.begin(), ord.end(),
@@ -441,11 +513,13 @@ int eig_lowrank(mlff_ctx *ctx, int64_t k, int mask_mode, int64_t dim_i, double *
       MLFF_HIP(ctx, hipStreamSynchronize(s));
       double worst = 0.0;
       for (int64_t j = 0; j < k; ++j) worst = std::max(worst, std::sqrt(std::max(res[j], 0.0)));
-      converged = worst <= kEigTol * std::fabs(theta[0]) || full;
+      const bool met = worst <= kEigTol * std::fabs(theta[0]);
+      converged = full || (q_orth && met && (polished || it == kEigMaxIter));
+      polished = polished || met;
     }
     if (!converged) {  // Q <- orth(S Q)
       MLFF_HIP(ctx, hipMemcpyAsync(Q, Y, sizeof(double) * panel, hipMemcpyDeviceToDevice, s));
-      MLFF_TRY(chol_qr3(ctx, Q, b, blk, G));
+      MLFF_TRY(chol_qr3(ctx, Q, b, blk, G, &q_orth));
     }
   }
   {
@@ -515,7 +589,8 @@ int spectrum(mlff_ctx *ctx, bool preconditioned, double *eig_out) {
   if (preconditioned && ctx->precon_kind == MLFF_PRECON_NONE) preconditioned = false;
   MLFF_TRY(operator_prepare(ctx));
   ScratchScope scope(ctx);
-  double *Y = nullptr, *A = nullptr, *V = nullptr, *x = nullptr;
+  double *Y = nullptr, *A = nullptr, *V = nullptr, *x = nullptr, *rq = nullptr;
+  MLFF_TRY(scratch_alloc(ctx, &rq, (size_t)n));
   MLFF_TRY(scratch_alloc(ctx, &Y, (size_t)round_up(n, 8) * blk));
   MLFF_TRY(scratch_alloc(ctx, &A, (size_t)n * n));
   MLFF_TRY(scratch_alloc(ctx, &V, (size_t)n * n));
@@ -540,10 +615,9 @@ int spectrum(mlff_ctx *ctx, bool preconditioned, double *eig_out) {
     hipLaunchKernelGGL(k_symmetrize, dim3(grid1(n * n)), dim3(256), 0, s, A, (int)n);
     MLFF_HIP(ctx, hipGetLastError());
   }
-  MLFF_TRY(jacobi_eigh(ctx, H, (int)n, V));
+  MLFF_TRY(jacobi_eigh(ctx, H, (int)n, V, rq));
   std::vector<double> d(n);
-  MLFF_HIP(ctx, hipMemcpy2DAsync(d.data(), sizeof(double), H, sizeof(double) * (n + 1), sizeof(double),
-                                 n, hipMemcpyDeviceToHost, s));
+  MLFF_HIP(ctx, hipMemcpyAsync(d.data(), rq, sizeof(double) * n, hipMemcpyDeviceToHost, s));
   MLFF_HIP(ctx, hipStreamSynchronize(s));
   const double sg = preconditioned ? ctx->sigma_p : 1.0;
   for (int64_t i = 0; i < n; ++i) d[i] *= sg;
