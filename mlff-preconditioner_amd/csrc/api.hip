@@ -944,9 +944,6 @@ int launch_iteration_ranks(mlff_ctx *ctx, long long it, std::vector<GemvMark> *m
   // symmetric tiles (dynamic schedule): p = z + beta p formed by the tile workgroups from the
   // gathered z and written by the slot reduction (k_update_p_gathered's bits, one launch less)
   const bool fuse_pg = ctx->fuse_p && ctx->use_sym && ctx->sym.dyn > 0 && ctx->sym.ntiles > 0;
-  // symmetric tiles + low-rank apply: k_update_xr_shares folded into the next T r pass
-  const bool fold_xr = ctx->fuse_xr_ranks && ctx->use_sym && lowrank &&
-                       xr_fold_fits(ctx->blk, ctx->tsplit, ctx->nrows);
   PGather pg;
   if (fuse_pg)
     pg = PGather{ctx->gb, ctx->gstride, ctx->blk, ctx->world, ctx->st, it};
@@ -964,10 +961,9 @@ int launch_iteration_ranks(mlff_ctx *ctx, long long it, std::vector<GemvMark> *m
     c0 = mark_begin(ctx, marks);
     MLFF_TRY(comm_reduce_scatter(ctx, sp.yg, sp.yr, (size_t)sp.ystride));
     mark_end(ctx, marks, c0, it, 2);
-    if (!fold_xr)
-      launch_update_xr_shares(ctx->x, ctx->r, p_loc, sp.yr, sp.yr + ctx->blk, ctx->world,
-                              ctx->nrows, ctx->sigma_K, ctx->lam,
-                              lowrank ? ctx->tpart_base : rr_part(ctx), ctx->st, status, s);
+    launch_update_xr_shares(ctx->x, ctx->r, p_loc, sp.yr, sp.yr + ctx->blk, ctx->world, ctx->nrows,
+                            ctx->sigma_K, ctx->lam, lowrank ? ctx->tpart_base : rr_part(ctx),
+                            ctx->st, status, s);
   } else {
     MLFF_TRY(launch_operator(ctx, ctx->p_full, ctx->q, p_loc, status, pq_part(ctx)));
     mark_end(ctx, marks, e0, it);
@@ -982,17 +978,7 @@ int launch_iteration_ranks(mlff_ctx *ctx, long long it, std::vector<GemvMark> *m
     // z half, kind 1) so a sampled apply is always timed whole
     ctx->timing.sample = (it + 1) % ctx->timing.every == 0;
     const size_t tm = mark_begin(ctx, marks);
-    if (fold_xr) {
-      // x, r update of this iteration inside the T r pass: r_new goes to the other buffer
-      // (ctx->z, unused by the sharded iteration), which becomes r
-      launch_gemv_xr(ctx->T, ctx->blk, ctx->k, ctx->blk, ctx->tsplit, ctx->r, ctx->z, ctx->x, p_loc,
-                     ctx->sym.yr, ctx->sym.yr + ctx->blk, ctx->world, ctx->nrows, ctx->sigma_K,
-                     ctx->lam, ctx->tpart_base, ctx->st, ctx->tpart, status, s);
-      std::swap(ctx->r, ctx->z);
-    } else {
-      launch_gemv_split(ctx->T, ctx->blk, ctx->k, ctx->blk, ctx->tsplit, ctx->r, ctx->tpart, status,
-                        s);
-    }
+    launch_gemv_split(ctx->T, ctx->blk, ctx->k, ctx->blk, ctx->tsplit, ctx->r, ctx->tpart, status, s);
     mark_end(ctx, marks, tm, it, 3);
     c0 = mark_begin(ctx, marks);
     MLFF_TRY(allreduce(ctx, ctx->tpart_base, (size_t)(kVecGrid + ctx->k * ctx->tsplit)));
@@ -1248,7 +1234,6 @@ int mlff_ctx_create(int device, int rank, int world, const unsigned char *comm_i
     const char *e = std::getenv(name);
     *flag = e == nullptr || std::atoi(e) != 0;
   }
-  if (const char *e = std::getenv("MLFF_FUSE_XR_RANKS")) ctx->fuse_xr_ranks = std::atoi(e) != 0;
   if (const char *e = std::getenv("MLFF_PQ_PUBLISH")) ctx->pq_publish = std::atoi(e) != 0;
   if (const char *e = std::getenv("MLFF_WB_REFINE")) ctx->wb_refine = std::max(0, std::atoi(e));
   if (const char *e = std::getenv("MLFF_NYS_REFINE")) ctx->nys_refine = std::atoi(e) != 0;

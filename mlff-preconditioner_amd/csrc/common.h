@@ -509,9 +509,6 @@ struct mlff_ctx {
   // MLFF_FUSE_P / MLFF_FUSE_XR (=0: separate launches) when the context is created
   bool fuse_p = true, fuse_xr = true;
   bool cho_fast = true;  // cho_factor_stable: shifted Cholesky first inside builds (MLFF_CHO_FAST)
-  // sharded tiled iteration: k_update_xr_shares folded into the next T r pass (MLFF_FUSE_XR_RANKS=1;
-  // off by default: SOLO floors 4.5 us slower at W = 4, equal at W = 8)
-  bool fuse_xr_ranks = false;
   bool pq_publish = false;       // MLFF_PQ_PUBLISH=1: the separate k_pq_publish launch (A/B)
   bool piv_persist_off = false;  // the persistent pivoted Cholesky timed out once (kernels_pivchol.hip)
   // Woodbury panel re-orthogonalised by a second CholeskyQR step (MLFF_WB_REFINE, woodbury_inplace;
@@ -707,11 +704,6 @@ void launch_update_p_gathered(const double *gb, int64_t gstride, int64_t blk, in
 void launch_update_xr_shares(double *x, double *r, const double *p, const double *y,
                              const double *shares, int world, int64_t n, double sigma, double lam,
                              double *rr_part, DevState *st, const int *status, hipStream_t s);
-// launch_update_xr_shares folded into the T r pass of the next apply (launch_gemv_split's
-// tpart): r_new = r - alpha q into r_out (the caller swaps r and r_out), x, the rr partials
-// and T r_new, the bits of the two launches; xr_fold_fits: the split / row-count shapes it
-// covers
-bool xr_fold_fits(int64_t ncols, int splits, int64_t n);
 // kernels_dd.hip (MLFF_EXACT_SUMS): y = sigma fl(M v) + lam vloc with double-double row sums;
 // z = sigma_p lam_inv (r - fl(T^T fl(T r))) with double-double dot products (t: k doubles)
 void launch_dd_gemv_rows(const double *M, int64_t ld, int64_t rows, int64_t ncols, const double *v,
@@ -725,11 +717,6 @@ void launch_dd_lowrank(const double *T, int64_t ldt, int64_t k, const double *r,
 // double-double.  The Woodbury panel's Gram matrices (MLFF_WB_GRAM)
 int gram_wide_dd(mlff_ctx *ctx, const double *W, int64_t k, int64_t ncols, int64_t ldw, double *G,
                  bool exact_products);
-void launch_gemv_xr(const double *T, int64_t ldt, int64_t k, int64_t ncols, int splits,
-                    const double *r, double *r_out, double *x, const double *p, const double *y,
-                    const double *shares, int world, int64_t n, double sigma, double lam,
-                    double *rr_part, DevState *st, double *tpart, const int *status,
-                    hipStream_t s);
 // pq = sum(pq_part); alpha = rho/pq; x += alpha p; r -= alpha q; rr partials
 void launch_update_xr(double *x, double *r, const double *p, const double *q, int64_t n,
                       const double *pq_part, double *rr_part, DevState *st, const int *status,

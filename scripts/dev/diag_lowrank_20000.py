@@ -1,6 +1,6 @@
 """The random-panel solve of tests/test_gpu_core.py::test_one_pass_lowrank_apply[20000-400-0] on the
 GPU with the one-pass (cluster) apply and with two passes: traces saved for comparison with the
-CPU orders of scripts/dev/lowrank_chaotic_band.py (run under MLFF_LC_CFG to pick the cluster form).
+CPU orders of scripts/dev/lowrank_chaotic_band.py.
 
     python scripts/dev/diag_lowrank_20000.py gpurun_out/r04/lr20000_<tag>.npz
 """

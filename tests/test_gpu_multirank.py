@@ -83,14 +83,21 @@ def gather(outs, key):
     return np.concatenate([o[key] for o in outs])
 
 
+SHARDED_CASES = [
+    (2, "none", "auto", 1003), (3, "none", "auto", 1003), (2, "nystrom", "auto", 1003),
+    (3, "nystrom", "auto", 1003), (2, "pivchol", "auto", 1003), (3, "pivchol", "auto", 1003),
+    (2, "none", "dense", 1003), (3, "pivchol", "dense", 1003), (8, "nystrom", "auto", 1003),
+    (8, "none", "dense", 1003), (2, "nystrom", "auto", 9000), (3, "pivchol", "auto", 9000)]
+
+
 @pytest.mark.timeout(600)
-@pytest.mark.parametrize("world,precon,storage", [
-    (2, "none", "auto"), (3, "none", "auto"), (2, "nystrom", "auto"), (3, "nystrom", "auto"),
-    (2, "pivchol", "auto"), (3, "pivchol", "auto"), (2, "none", "dense"),
-    (3, "pivchol", "dense"), (8, "nystrom", "auto"), (8, "none", "dense")])
-def test_sharded_solve_matches_single_rank(world, precon, storage):
-    """auto = symmetric tiles (reduce-scatter of the partial products), dense = row GEMV."""
-    n = 1003
+@pytest.mark.parametrize("world,precon,storage,n", SHARDED_CASES,
+                         ids=[f"{w}-{p}-{s}" + (f"-{n}" if n != 1003 else "")
+                              for w, p, s, n in SHARDED_CASES])
+def test_sharded_solve_matches_single_rank(world, precon, storage, n):
+    """auto = symmetric tiles (reduce-scatter of the partial products), dense = row GEMV.
+    n = 9000 runs the low-rank apply's T r pass in 6-9 column splits (n = 1003: one); chunk = 5
+    puts iterations gated after the stop test inside chunks."""
     ref = run_ranks(1, lambda r, w, key: solve_case(r, w, key, n, precon, storage=storage))[0]
     outs = run_ranks(world, lambda r, w, key: solve_case(r, w, key, n, precon, storage=storage))
     spans = [o["r"] for o in outs]
@@ -112,10 +119,12 @@ def test_sharded_solve_matches_single_rank(world, precon, storage):
     np.testing.assert_allclose(outs[0]["lev"], ref["lev"], rtol=1e-8, atol=1e-12)
     assert outs[0]["info"] == ref["info"] == 0
     # W ranks vs one rank: two samples of the summation-order distribution whose spread the
-    # oracle measured on this very system (noise_band.json "rbf_n1003/<precon>")
-    band = noise_band(f"rbf_n1003/{'none' if precon == 'none' else precon}")
-    assert_pcg_parity(outs[0]["iters"], outs[0]["trace"][1:], gather(outs, "x"), ref["iters"],
-                      ref["trace"][1:], ref["x"], band=band)
+    # oracle measured on this very system (noise_band.json "rbf_n1003/<precon>": recorded for
+    # n = 1003 only)
+    if n == 1003:
+        band = noise_band(f"rbf_n1003/{'none' if precon == 'none' else precon}")
+        assert_pcg_parity(outs[0]["iters"], outs[0]["trace"][1:], gather(outs, "x"), ref["iters"],
+                          ref["trace"][1:], ref["x"], band=band)
 
 
 @pytest.mark.timeout(300)
@@ -207,28 +216,6 @@ def test_sharded_pq_arrival_ordered_bitwise(world, monkeypatch):
         assert a["iters"] == b["iters"] and a["info"] == b["info"] == 0
         np.testing.assert_array_equal(a["trace"], b["trace"])
         np.testing.assert_array_equal(a["x"], b["x"])
-
-
-@pytest.mark.timeout(600)
-@pytest.mark.parametrize("world,precon,n", [(2, "nystrom", 1003), (3, "pivchol", 1003),
-                                            (8, "nystrom", 1003), (2, "nystrom", 9000),
-                                            (3, "pivchol", 9000)])
-def test_sharded_fused_xr_update_bitwise(world, precon, n, monkeypatch):
-    """The sharded tiled iteration with k_update_xr_shares folded into the next apply's T r
-    pass (k_gemv_xr: r_new staged in LDS, x / r / rr partials written by row group 0, r and
-    the spare vector swapped; MLFF_FUSE_XR_RANKS=1) against the separate launch (default):
-    the same arithmetic, so iterates, residual curve and stop decisions are bit-identical.
-    n = 9000 runs the T r pass in 6-9 column splits (n = 1003: one); chunk = 5 puts
-    iterations gated after the stop test inside chunks."""
-    out = {}
-    for fuse in ("1", "0"):
-        monkeypatch.setenv("MLFF_FUSE_XR_RANKS", fuse)
-        out[fuse] = run_ranks(world, lambda r, w, key: solve_case(r, w, key, n, precon))
-    for a, b in zip(out["1"], out["0"]):
-        assert a["iters"] == b["iters"] and a["info"] == b["info"] == 0
-        np.testing.assert_array_equal(a["trace"], b["trace"])
-        np.testing.assert_array_equal(a["x"], b["x"])
-        np.testing.assert_array_equal(a["lev"], b["lev"])
 
 
 @pytest.mark.timeout(300)

@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 
 CASE_IDS = [sh.case_id(c) for c in sh.CASES]
 PT_MAX_ATOMS = 24          # csrc/kernels_pt.hip kPtVariants: D <= 288
-PT_CAPACITY = [36, 72, 112, 224, 288, 36, 36, 40, 40, 36, 36, 36, 36, 36, 36, 36, 36]  # L x DL
+PT_CAPACITY = [36, 72, 112, 224, 288]  # L x DL
 PRED_TILE_MAX_D = 288
 
 
@@ -105,7 +105,7 @@ def _matvec(sg, c, want_form, E=False):
 @pytest.mark.parametrize("form", ["pair", "rec", "pt"])
 def test_operator(sg, c, form, monkeypatch):
     monkeypatch.setenv("MLFF_MF_FORM", form)
-    for v in ("MLFF_PT_VARIANT", "MLFF_PT_CHUNKS", "MLFF_PT_MFMA", "MLFF_REC_RG", "MLFF_MF_REC"):
+    for v in ("MLFF_PT_VARIANT", "MLFF_PT_CHUNKS", "MLFF_REC_RG", "MLFF_MF_REC"):
         monkeypatch.delenv(v, raising=False)
     # the one exception: no pair-tile form past 24 atoms, the request falls to the record form
     want = "rec" if form == "pt" and c.n > PT_MAX_ATOMS else form
