@@ -288,6 +288,19 @@ int mlff_predict(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, doubl
  * (measurement). */
 int mlff_predict_info(mlff_ctx *ctx, int *form_out, int64_t *slab_out, double *flops_per_query_out,
                       double *bytes_per_query_out);
+/* The analytic Hessian d2E / dR2 of the model set by mlff_predict_set_model (with the energy
+ * coefficients, if any) at the geometries R (Q x n_atoms x 3): H_out (Q x 3 n_atoms x 3 n_atoms),
+ * in the model's [E] / [R]^2, std included.  No reference counterpart: the reference has no
+ * Hessian; the formulas (the second derivative of mlff_predict's closed form) are at the head of
+ * csrc/kernels_predict_hess.hip.  H_out[q] equals its transpose bit for bit, and every query's
+ * result has the same bits whatever the batch it arrives in.  The slab buffers are allocated by
+ * the first call (MLFF_ERR_NOMEM if they cannot be; MLFF_PRED_SLAB bounds the queries per pass
+ * here too).  MLFF_ERR_STATE before a model is set; Q = 0 is MLFF_OK. */
+int mlff_predict_hessian(mlff_ctx *ctx, const double *R, int64_t Q, double *H_out);
+/* The algorithmic work of one Hessian: flops of its pair stage and of the prediction's (which
+ * supplies dE / d descriptor), and bytes of the two streams of the training rows (derivation at
+ * pred_hess_work, csrc/kernels_predict_hess.hip).  No reference counterpart (measurement). */
+int mlff_predict_hessian_info(mlff_ctx *ctx, double *flops_per_query_out, double *bytes_per_query_out);
 
 int mlff_set_operator(mlff_ctx *ctx, double sigma_K, double lam);
 /* y_local = A v_global (v_global has N entries).  Collective over the ranks

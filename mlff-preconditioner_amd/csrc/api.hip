@@ -1710,6 +1710,32 @@ int mlff_predict_info(mlff_ctx *ctx, int *form_out, int64_t *slab_out, double *f
   MLFF_API_END(ctx)
 }
 
+int mlff_predict_hessian(mlff_ctx *ctx, const double *R, int64_t Q, double *H_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  if (ctx->world > 1) return set_error(ctx, MLFF_ERR_ARG, "predict hessian: runs on a one-rank context");
+  if (!ctx->pred.ready)
+    return set_error(ctx, MLFF_ERR_STATE, "predict hessian: no model set (mlff_predict_set_model)");
+  if (Q < 0) return set_error(ctx, MLFF_ERR_ARG, "predict hessian: Q < 0");
+  if (Q == 0) return MLFF_OK;
+  if (R == nullptr || H_out == nullptr) return set_error(ctx, MLFF_ERR_ARG, "predict hessian: null pointer");
+  return pred_hess_run(ctx, R, Q, H_out);
+  MLFF_API_END(ctx)
+}
+
+int mlff_predict_hessian_info(mlff_ctx *ctx, double *flops_per_query_out, double *bytes_per_query_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  if (!ctx->pred.ready)
+    return set_error(ctx, MLFF_ERR_STATE, "predict hessian: no model set (mlff_predict_set_model)");
+  double fl = 0.0, by = 0.0;
+  pred_hess_work(ctx->pred, &fl, &by);
+  if (flops_per_query_out) *flops_per_query_out = fl;
+  if (bytes_per_query_out) *bytes_per_query_out = by;
+  return MLFF_OK;
+  MLFF_API_END(ctx)
+}
+
 int mlff_set_operator(mlff_ctx *ctx, double sigma_K, double lam) {
   MLFF_API_BEGIN
   MLFF_ENTER(ctx);

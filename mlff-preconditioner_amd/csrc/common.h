@@ -211,6 +211,19 @@ struct PredData {
   double *Fd = nullptr;                     // slab x D
   double *EF = nullptr;                     // results of a slab: E (slab) then F (slab x 3 n)
   double *h_in = nullptr, *h_out = nullptr; // pinned staging of Rq and EF: one copy each way
+  // Hessians (kernels_predict_hess.hip): allocated by the first mlff_predict_hessian
+  bool hs_ready = false;
+  int hs_S = 1;                             // chunks of the (j, p) range: fixed by MP
+  int hs_tb = 1;                            // rows per step of the pair stage: fixed by n
+  int hs_stage = 0;                         // > 0: the staged pair stage (k_hs_pair_s) with this many rows
+  bool hs_fd = false;                       // the Hessian's pair stage forms Fd itself (D <= 512)
+  int64_t hs_slab = 0;                      // queries per pass (<= slab)
+  int64_t hs_nblk = 0;                      // 4 x 4 blocks of the lower triangle of H
+  int64_t hs_PS = 0;                        // row of the partials: 16 hs_nblk + 2 (+ D for Fd)
+  double *hs_part = nullptr;                // hs_S x hs_slab x hs_PS chunk partials
+  double *hs_sum = nullptr;                 // hs_slab x hs_PS
+  double *hs_H = nullptr;                   // hs_slab x 3n x 3n
+  double *hs_h_out = nullptr;               // pinned staging of hs_H
 };
 
 // Synthetic RBF kernel source (tools/utils.py:173-187): the points, scaled by 1 / length
@@ -933,6 +946,17 @@ int pred_run(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F
 bool pred_tile_supported(int64_t D);
 void pred_work(const PredData &pd, double *flops_per_query, double *bytes_per_query);
 void pred_free(PredData &pd);
+// upload nq <= pred.slab host geometries and run the descriptor stage and, with_fd, the pair and
+// chunk-sum stages: pred.Rq, Rdq, Rddq (and Fd) of those queries are then on the device (in
+// stream order)
+int pred_fd_slab(mlff_ctx *ctx, const double *R, int64_t nq, bool with_fd);
+
+// ---- Hessians of the held model (kernels_predict_hess.hip) -------------------
+// H (Q x 3n x 3n) of the Q host geometries R; the slab buffers are allocated by the first call
+// (MLFF_PRED_HESS_SLAB is read there)
+int pred_hess_run(mlff_ctx *ctx, const double *R, int64_t Q, double *H_out);
+void pred_hess_work(const PredData &pd, double *flops_per_query, double *bytes_per_query);
+void pred_hess_free(PredData &pd);
 
 // ---- operator access for the builds (api.hip) --------------------------------
 // require the operator and resolve its storage (builds the tiles if they are to be used)

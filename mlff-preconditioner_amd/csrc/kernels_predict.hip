@@ -492,6 +492,7 @@ int pr_alloc(mlff_ctx *ctx, T **p, int64_t count) {
 }  // namespace
 
 void pred_free(PredData &pd) {
+  pred_hess_free(pd);
   for (double *p : {pd.Rt, pd.Zt, pd.Et, pd.Rq, pd.Rdq, pd.Rddq, pd.part, pd.Fd, pd.EF})
     if (p != nullptr) (void)hipFree(p);
   for (double *p : {pd.h_in, pd.h_out})
@@ -613,15 +614,16 @@ int pred_set_energy_coefficients(mlff_ctx *ctx, const double *alphas_E) {
   return MLFF_OK;
 }
 
-int pred_run(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F_out) {
-  const PredData &pd = ctx->pred;
-  hipStream_t s = ctx->stream;
-  const int64_t n3 = 3 * (int64_t)pd.n, D = pd.D;
+// descriptors of the nq queries in pd.Rq (Rdq, Rddq of the slab) and, with_fd, the pair stage
+// and the chunk sum (Fd of the slab)
+static void pr_launch_fd(const PredData &pd, int64_t nq, bool with_fd, hipStream_t s) {
+  const int64_t D = pd.D;
   PrArgs a;
   a.Rdq = pd.Rdq;
   a.Rt = pd.Rt;
   a.Zt = pd.Zt;
   a.D = D;
+  a.nq = nq;
   a.MP = pd.MP;
   a.S = pd.S;
   a.sig = pd.sig;
@@ -634,26 +636,42 @@ int pred_run(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F
   a.Et = pd.Et;
   a.inv_3sig = 1.0 / (3.0 * pd.sig);
   const bool ecstr = pd.Et != nullptr;
+  const unsigned gx = (unsigned)std::min<int64_t>((D + 255) / 256, 64);
+  hipLaunchKernelGGL(k_pr_desc, dim3(gx, (unsigned)nq), dim3(256), 0, s, pd.Rq, pd.n, pd.Rdq, pd.Rddq);
+  if (!with_fd) return;
+  if (pd.form == 0) {
+    const PrVariant *v = pr_variant(D);
+    hipLaunchKernelGGL(ecstr ? v->fn_e : v->fn,
+                       dim3((unsigned)((nq + pd.G - 1) / pd.G), (unsigned)pd.S), dim3(kPrThreads),
+                       0, s, a);
+  } else {
+    hipLaunchKernelGGL(ecstr ? k_pr_stream<true> : k_pr_stream<false>,
+                       dim3((unsigned)((nq + kPrQB - 1) / kPrQB), (unsigned)pd.S), dim3(256), 0, s,
+                       a);
+  }
+  hipLaunchKernelGGL(k_pr_sum, dim3((unsigned)((D + 1 + kPrSumE - 1) / kPrSumE), (unsigned)nq),
+                     dim3(256), 0, s, pd.part, pd.PS, pd.ecol, D, nq, pd.S, pd.std, pd.c, pd.Fd, pd.EF);
+}
+
+int pred_fd_slab(mlff_ctx *ctx, const double *R, int64_t nq, bool with_fd) {
+  const PredData &pd = ctx->pred;
+  hipStream_t s = ctx->stream;
+  const int64_t n3 = 3 * (int64_t)pd.n;
+  // through the pinned staging buffer: one asynchronous copy per slab
+  std::memcpy(pd.h_in, R, sizeof(double) * nq * n3);
+  MLFF_HIP(ctx, hipMemcpyAsync(pd.Rq, pd.h_in, sizeof(double) * nq * n3, hipMemcpyHostToDevice, s));
+  pr_launch_fd(pd, nq, with_fd, s);
+  MLFF_HIP(ctx, hipGetLastError());
+  return MLFF_OK;
+}
+
+int pred_run(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F_out) {
+  const PredData &pd = ctx->pred;
+  hipStream_t s = ctx->stream;
+  const int64_t n3 = 3 * (int64_t)pd.n, D = pd.D;
   for (int64_t q0 = 0; q0 < Q; q0 += pd.slab) {
     const int64_t nq = std::min<int64_t>(pd.slab, Q - q0);
-    a.nq = nq;
-    // through the pinned staging buffers: one asynchronous copy each way per slab
-    std::memcpy(pd.h_in, R + q0 * n3, sizeof(double) * nq * n3);
-    MLFF_HIP(ctx, hipMemcpyAsync(pd.Rq, pd.h_in, sizeof(double) * nq * n3, hipMemcpyHostToDevice, s));
-    const unsigned gx = (unsigned)std::min<int64_t>((D + 255) / 256, 64);
-    hipLaunchKernelGGL(k_pr_desc, dim3(gx, (unsigned)nq), dim3(256), 0, s, pd.Rq, pd.n, pd.Rdq, pd.Rddq);
-    if (pd.form == 0) {
-      const PrVariant *v = pr_variant(D);
-      hipLaunchKernelGGL(ecstr ? v->fn_e : v->fn,
-                         dim3((unsigned)((nq + pd.G - 1) / pd.G), (unsigned)pd.S), dim3(kPrThreads),
-                         0, s, a);
-    } else {
-      hipLaunchKernelGGL(ecstr ? k_pr_stream<true> : k_pr_stream<false>,
-                         dim3((unsigned)((nq + kPrQB - 1) / kPrQB), (unsigned)pd.S), dim3(256), 0, s,
-                         a);
-    }
-    hipLaunchKernelGGL(k_pr_sum, dim3((unsigned)((D + 1 + kPrSumE - 1) / kPrSumE), (unsigned)nq),
-                       dim3(256), 0, s, pd.part, pd.PS, pd.ecol, D, nq, pd.S, pd.std, pd.c, pd.Fd, pd.EF);
+    MLFF_TRY(pred_fd_slab(ctx, R + q0 * n3, nq, true));
     hipLaunchKernelGGL(k_pr_jt, dim3((unsigned)((n3 + 63) / 64), (unsigned)nq), dim3(64), 0, s, pd.Rddq,
                        pd.Fd, pd.n, D, pd.std, pd.EF + nq);
     MLFF_HIP(ctx, hipGetLastError());

@@ -12,6 +12,9 @@ The model arrays go to the device once (`mlff_predict_set_model`,
 the geometries and gets E (Q,) and F (Q, 3n) back (`mlff_predict`, csrc/kernels_predict.hip).
 A query's result has the same bits whatever batch it is part of, so splitting a batch over
 `devices=[...]` (contiguous blocks, one context and one thread per entry) changes nothing.
+
+`gdml.hessian(R)` returns the analytic second derivative d2E / dR2, (Q, 3n, 3n), with the same
+guarantees (`mlff_predict_hessian`, csrc/kernels_predict_hess.hip); the reference has none.
 """
 from __future__ import annotations
 
@@ -213,6 +216,20 @@ class GDMLPredict:
         blocks = split_blocks(Q, len(self._engines))
         parts = self._all(lambda r: self._engines[r].predict(R[blocks[r][0]:blocks[r][1]]))
         return (np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts]))
+
+    def hessian(self, R) -> np.ndarray:
+        """The analytic Hessian d2E / dR2 at the geometries R (the shapes `predict` accepts):
+        (Q, 3 n_atoms, 3 n_atoms) in the model's [E] / [R]^2, each H[q] exactly symmetric
+        (`mlff_predict_hessian`, csrc/kernels_predict_hess.hip).  The reference has no Hessian;
+        the bits of a query's result do not depend on the batch or on the device split."""
+        if not self._engines:
+            raise RuntimeError("GDMLPredict is closed")
+        R = normalize_geometries(R, self.n_atoms)
+        if self._workers is None:
+            return self._engines[0].predict_hessian(R)
+        blocks = split_blocks(R.shape[0], len(self._engines))
+        parts = self._all(lambda r: self._engines[r].predict_hessian(R[blocks[r][0]:blocks[r][1]]))
+        return np.concatenate(parts)
 
     def close(self):
         """Release the device contexts and stop the workers (idempotent)."""

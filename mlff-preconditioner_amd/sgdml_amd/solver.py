@@ -229,6 +229,27 @@ class KernelSolver:
                    ctypes.byref(by))
         return {0: "tile", 1: "stream"}[form.value], slab.value, fl.value, by.value
 
+    def predict_hessian(self, R: np.ndarray) -> np.ndarray:
+        """H (Q, 3 n_atoms, 3 n_atoms) = d2E / dR2 of the geometries R (Q x n_atoms x 3) with the
+        model set by `predict_set_model`, energy coefficients included (mlff_predict_hessian;
+        the reference has no Hessian).  Units [E] / [R]^2 of the model; H[q] == H[q].T exactly."""
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        n = getattr(self, "_pred_n_atoms", None)
+        if n is not None and (R.ndim != 3 or R.shape[1:] != (n, 3)):
+            raise ValueError(f"R must be Q x {n} x 3, got {R.shape}")
+        if n is None and (R.ndim != 3 or R.shape[2] != 3):
+            raise ValueError("R must be Q x n_atoms x 3")
+        Q, n = R.shape[0], R.shape[1]
+        H = np.empty((Q, 3 * n, 3 * n))
+        self._call("mlff_predict_hessian", nat.dptr(R), int(Q), nat.dptr(H))
+        return H
+
+    def predict_hessian_info(self) -> tuple[float, float]:
+        """(flops, streamed bytes) of one Hessian (mlff_predict_hessian_info)."""
+        fl, by = ctypes.c_double(), ctypes.c_double()
+        self._call("mlff_predict_hessian_info", ctypes.byref(fl), ctypes.byref(by))
+        return fl.value, by.value
+
     def set_operator(self, sigma_K: float, lam: float):
         self._call("mlff_set_operator", float(sigma_K), float(lam))
 
