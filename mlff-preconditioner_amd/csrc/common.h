@@ -642,6 +642,13 @@ template <typename T>
 int scratch_alloc(mlff_ctx *ctx, T **out, size_t count) {
   return scratch_get(ctx, sizeof(T) * (count > 0 ? count : 1), reinterpret_cast<void **>(out));
 }
+// device memory that outlives the call; failure: *p = nullptr, "<what>: device allocation failed"
+template <typename T>
+int dev_alloc(mlff_ctx *ctx, T **p, int64_t count, const char *what) {
+  if (hipMalloc(p, sizeof(T) * (size_t)(count > 0 ? count : 1)) == hipSuccess) return MLFF_OK;
+  *p = nullptr;
+  return set_error(ctx, MLFF_ERR_NOMEM, std::string(what) + ": device allocation failed");
+}
 
 // ---- collectives (api.hip): RCCL, or the in-process transport ---------------
 // sum-allreduce of n doubles in place (no-op on one rank)

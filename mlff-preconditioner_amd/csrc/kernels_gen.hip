@@ -161,7 +161,7 @@ void launch_gather_mm(const double *W, int64_t ldw, const int64_t *idx, int64_t 
 // where every Jacobian row d = pair(s, t) (s > t) has only two non-zero atoms:
 // J[d, t] = +Rdd[d], J[d, s] = -Rdd[d] (desc.py:444-462).
 
-// pair_idx / pair_sign: sgdml_col.h
+// pair_idx / pair_sign: sgdml_pair.h
 
 // The reference assembles the lower block triangle and mirrors it
 // (train.py:172-210, exploit_sym): block (i, j) = Blk(r=i, s=j) for j < i and
@@ -209,6 +209,7 @@ __global__ __launch_bounds__(256) void k_sgdml_uv(const double *__restrict__ Rd,
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
   __syncthreads();
   const double nrm2 = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+  // not matern_row (sgdml_pair.h) on purpose: the reference's rounding (tests/test_gpu_golden.py)
   const double sqrt5 = sqrt(5.0);
   const double norm = sqrt5 * sqrt(nrm2);
   const double mat52 = exp(-norm / sig) / (3.0 * sig * sig * sig * sig) * 5.0;
@@ -647,51 +648,28 @@ void launch_sgdml_columns(const double *Rdd, int64_t M, int n, int64_t D, int64_
 }
 
 // ---------------------------------------------------------------------------
-// Descriptors: R_desc[m, d] = 1 / |r_a - r_b|, R_d_desc[m, d, :] = (r_a - r_b) / |r_a - r_b|^3
-// for d = pair(a, b), a > b (desc.py:80-200 without cutoff / PBC).
-__global__ __launch_bounds__(256) void k_desc(const double *__restrict__ R, int64_t M, int n,
-                                              double *__restrict__ Rd, double *__restrict__ Rdd) {
-  const int64_t D = (int64_t)n * (n - 1) / 2;
-  const int64_t m = blockIdx.y;
-  const double *r = R + m * n * 3;
-  for (int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x; d < D;
-       d += (int64_t)gridDim.x * 256) {
-    // invert d = a(a-1)/2 + b
-    int a = (int)((1.0 + sqrt(1.0 + 8.0 * (double)d)) * 0.5);
-    while ((int64_t)a * (a - 1) / 2 > d) --a;
-    while ((int64_t)(a + 1) * a / 2 <= d) ++a;
-    const int b = (int)(d - (int64_t)a * (a - 1) / 2);
-    const double dx = r[a * 3 + 0] - r[b * 3 + 0];
-    const double dy = r[a * 3 + 1] - r[b * 3 + 1];
-    const double dz = r[a * 3 + 2] - r[b * 3 + 2];
-    const double dist = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
-    Rd[m * D + d] = 1.0 / dist;
-    const double d3 = dist * dist * dist;
-    Rdd[(m * D + d) * 3 + 0] = dx / d3;
-    Rdd[(m * D + d) * 3 + 1] = dy / d3;
-    Rdd[(m * D + d) * 3 + 2] = dz / d3;
-  }
-}
+// Descriptors R_desc, R_d_desc of the training set: k_desc_t (sgdml_pair.h), dist^3 by two products
+constexpr auto k_desc = k_desc_t<false>;
 
 int sgdml_descriptors(const double *R, int64_t M, int n, double *R_desc, double *R_d_desc) {
   const int64_t D = (int64_t)n * (n - 1) / 2;
   double *dR = nullptr, *dRd = nullptr, *dRdd = nullptr;
-  if (hipMalloc(&dR, sizeof(double) * M * n * 3) != hipSuccess) return MLFF_ERR_NOMEM;
-  if (hipMalloc(&dRd, sizeof(double) * M * D) != hipSuccess) return MLFF_ERR_NOMEM;
-  if (hipMalloc(&dRdd, sizeof(double) * M * D * 3) != hipSuccess) return MLFF_ERR_NOMEM;
-  if (hipMemcpy(dR, R, sizeof(double) * M * n * 3, hipMemcpyHostToDevice) != hipSuccess)
-    return MLFF_ERR_HIP;
-  const unsigned gx = (unsigned)std::min<int64_t>((D + 255) / 256, 64);
-  hipLaunchKernelGGL(k_desc, dim3(gx, (unsigned)M), dim3(256), 0, 0, dR, M, n, dRd, dRdd);
-  if (hipGetLastError() != hipSuccess) return MLFF_ERR_HIP;
-  if (hipMemcpy(R_desc, dRd, sizeof(double) * M * D, hipMemcpyDeviceToHost) != hipSuccess)
-    return MLFF_ERR_HIP;
-  if (hipMemcpy(R_d_desc, dRdd, sizeof(double) * M * D * 3, hipMemcpyDeviceToHost) != hipSuccess)
-    return MLFF_ERR_HIP;
-  hipFree(dR);
-  hipFree(dRd);
-  hipFree(dRdd);
-  return MLFF_OK;
+  const int rc = [&]() -> int {
+    if (hipMalloc(&dR, sizeof(double) * M * n * 3) != hipSuccess ||
+        hipMalloc(&dRd, sizeof(double) * M * D) != hipSuccess ||
+        hipMalloc(&dRdd, sizeof(double) * M * D * 3) != hipSuccess)
+      return MLFF_ERR_NOMEM;
+    if (hipMemcpy(dR, R, sizeof(double) * M * n * 3, hipMemcpyHostToDevice) != hipSuccess) return MLFF_ERR_HIP;
+    const unsigned gx = (unsigned)std::min<int64_t>((D + 255) / 256, 64);
+    hipLaunchKernelGGL(k_desc, dim3(gx, (unsigned)M), dim3(256), 0, 0, dR, n, dRd, dRdd);
+    if (hipGetLastError() != hipSuccess ||
+        hipMemcpy(R_desc, dRd, sizeof(double) * M * D, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(R_d_desc, dRdd, sizeof(double) * M * D * 3, hipMemcpyDeviceToHost) != hipSuccess)
+      return MLFF_ERR_HIP;
+    return MLFF_OK;
+  }();
+  for (double *p : {dR, dRd, dRdd}) (void)hipFree(p);  // the one exit (a null pointer is a no-op)
+  return rc;
 }
 
 }  // namespace mlff

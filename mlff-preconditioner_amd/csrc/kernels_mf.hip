@@ -28,6 +28,7 @@
 #include <cstdio>
 
 #include "common.h"
+#include "sgdml_pair.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -334,6 +335,7 @@ __global__ __launch_bounds__(256) void k_mf_pair_fin(const double *__restrict__ 
   for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
   if (lane != 0) return;
   if (MODE == 0) {
+    // not matern_row (sgdml_pair.h) on purpose: the reference's rounding (tests/test_gpu_golden.py)
     const double norm = sqrt(5.0) * sqrt(s);
     const double m = exp(-norm / sig) * 5.0 / (3.0 * sig * sig * sig * sig);
     out0[o] = 5.0 * m;
@@ -420,10 +422,6 @@ __global__ __launch_bounds__(64) void k_mf_h(const double *__restrict__ Rd,
       if (k < nk) F[(ic0 + k) * D + d] = h[k];
 }
 
-__device__ __forceinline__ int64_t pair_of(int a, int b) {
-  return a > b ? (int64_t)a * (a - 1) / 2 + b : (int64_t)b * (b - 1) / 2 + a;
-}
-
 // rows of this rank: g = i 3n + 3a + c,  y = sum_{b != a} sgn * Rdd_i[pair(a,b), c] F_i[pair(a,b)]
 // (J[pair, (t, c)] = +Rdd, J[pair, (s, c)] = -Rdd with s > t, desc.py:444-462).
 // Workgroup = (point, block of 32 atoms a, slice of partner blocks); it walks the
@@ -450,7 +448,7 @@ __device__ __forceinline__ void jt_load(const double *__restrict__ Fi,
     f[u] = 0.0;
     r[u][0] = r[u][1] = r[u][2] = 0.0;
     if (aa < n && bb < n && aa != bb) {
-      const int64_t d = pair_of(aa, bb);
+      const int64_t d = pair_idx(aa, bb);
       const double sg = aa > bb ? -1.0 : 1.0;
       f[u] = sg * Fi[d];
       r[u][0] = Ri[d * 3 + 0];

@@ -11,7 +11,8 @@
 //   E_q  = sum_jp a w                      (predict.py:207: a m' (nrm + sig)),  m' = sig m
 //   F_q  = J_q^T Fd_q                      (vec_dot_d_desc, desc.py:408-428)
 //   E = std E_q + c_int,  F = std F_q      (predict.py:1106-1108)
-// The pair arithmetic is k_pt_pair's (kernels_pt.hip) with one more fma per pair for the energy.
+// The pair arithmetic is k_pt_pair's with one more fma per pair for the energy: both take the row
+// scalars from matern_row (sgdml_pair.h).
 //
 // Energy-constrained models (use_E_cstr: alphas_E, predict.py:206-218, alphas_E_lin at :364-368)
 // add, with e_jp = alphas_E[j] and x = nrm / sig,
@@ -40,14 +41,15 @@
 //    stream.
 // Both write the chunk partials part[s][q][0 .. D) and the energy partial (column ecol), no
 // Q x M n_perms array.  k_pr_sum adds the S chunk partials of every entry in an order fixed by S
-// (16 groups of consecutive chunks in chunk order, then the groups in order), k_pr_jt forms
-// J_q^T Fd_q with the partners in increasing order (as k_pt_fin) and scales.
+// (chunk_sum, sgdml_pair.h), k_pr_jt forms J_q^T Fd_q with the partners in increasing order
+// (k_pt_fin's order, both through pair_idx) and scales.
 //
 // Determinism: no atomics; the chunk count S, the tile shape and every reduction order depend on
 // the model (M n_perms, D, form, constrained or not) only, and no sum runs across queries: a
 // query's E, F have the same bits whatever the batch, its position in it, the slab size or the
 // device split.
 #include "common.h"
+#include "sgdml_pair.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -64,9 +66,6 @@ constexpr int kPrQB = 4;            // stream form: queries per workgroup
 constexpr int kPrTB = 2;            // stream form: (j, p) rows per step (and per chunk: S = MP / 2)
 constexpr int kPrSU = 2;            // stream form: entries per thread in flight (d, d + 256)
 constexpr int kPrStreamMaxChunks = 4096;
-constexpr int kPrSumE = 16;         // k_pr_sum: entries per workgroup
-constexpr int kPrSumG = 16;         // k_pr_sum: chunk groups
-constexpr double kSqrt5 = 2.23606797749978969640917366873127623544;
 
 struct PrArgs {
   const double *Rdq;  // nq x D query descriptors
@@ -74,39 +73,15 @@ struct PrArgs {
   const double *Zt;   // MP x D
   int64_t D, nq, MP;
   int S;              // chunks of the (j, p) range (gridDim.y)
-  double sig, sig2, inv_sig, k5;  // k5 = 5 / (3 sig^4)
+  MaternConsts mc;    // sgdml_pair.h
   double *part;       // S x nq x PS
   int64_t PS, ecol;   // row stride of part and the column of the energy partial
   const double *Et;   // MP energy coefficients alphas_E[j] (ECSTR kernels only)
   double inv_3sig;    // 1 / (3 sig)
 };
 
-// Desc.from_R for the queries (k_desc's arithmetic, kernels_gen.hip) on the context's stream
-__global__ __launch_bounds__(256) void k_pr_desc(const double *__restrict__ R, int n,
-                                                 double *__restrict__ Rd, double *__restrict__ Rdd) {
-  const int64_t D = (int64_t)n * (n - 1) / 2;
-  const int64_t m = blockIdx.y;
-  const double *r = R + m * n * 3;
-  for (int64_t d = (int64_t)blockIdx.x * 256 + threadIdx.x; d < D; d += (int64_t)gridDim.x * 256) {
-    int a = (int)((1.0 + sqrt(1.0 + 8.0 * (double)d)) * 0.5);
-    while ((int64_t)a * (a - 1) / 2 > d) --a;
-    while ((int64_t)(a + 1) * a / 2 <= d) ++a;
-    const int b = (int)(d - (int64_t)a * (a - 1) / 2);
-    const double dx = r[a * 3 + 0] - r[b * 3 + 0];
-    const double dy = r[a * 3 + 1] - r[b * 3 + 1];
-    const double dz = r[a * 3 + 2] - r[b * 3 + 2];
-    const double dist = sqrt(__dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz)));
-    Rd[m * D + d] = 1.0 / dist;
-    // dist^3 rounded once, as the reference's pdist ** 3 (pow): the products' rounding errors
-    // (fma residuals) are added back
-    const double p2 = dist * dist, e2 = fma(dist, dist, -p2);
-    const double p3 = p2 * dist, e3 = fma(p2, dist, -p3);
-    const double d3 = p3 + fma(e2, dist, e3);
-    Rdd[(m * D + d) * 3 + 0] = dx / d3;
-    Rdd[(m * D + d) * 3 + 1] = dy / d3;
-    Rdd[(m * D + d) * 3 + 2] = dz / d3;
-  }
-}
+// Desc.from_R for the queries on the context's stream: k_desc_t (sgdml_pair.h), dist^3 rounded once
+constexpr auto k_pr_desc = k_desc_t<true>;
 
 // rows of Rt / Zt per LDS tile: 16, fewer for long descriptors (<= 9 KB per array: half of
 // k_pt_pair's tile for half its threads, so the staging registers per thread stay the same)
@@ -205,15 +180,13 @@ void k_pr_pair(PrArgs a) {
         ab = fma(d1, zv.y, ab);
       }
       const double rs = group_sum<L>(r2a + r2b), as = group_sum<L>(aa + ab);
-      const double nrm = kSqrt5 * sqrt(rs);
-      const double ex = exp(-nrm * a.inv_sig);
-      const double m = ex * a.k5;
-      const double w = fma(a.sig, nrm, a.sig2) * m;
-      double c = 5.0 * m * as;
+      const MaternRow mr = matern_row(rs, a.mc);
+      const double w = mr.w;
+      double c = 5.0 * mr.m * as;
       en = fma(as, w, en);
       if (ECSTR) {
         const double ej = sE[j];
-        const double kee = fma(nrm * a.inv_sig, fma(nrm, a.inv_3sig, 1.0), 1.0) * ex;
+        const double kee = kee_of(mr.nrm, mr.ex, a.mc.inv_sig, a.inv_3sig);
         c = fma(ej, w, c);
         en = fma(ej, kee, en);
       }
@@ -332,15 +305,13 @@ __global__ __launch_bounds__(256) void k_pr_stream(PrArgs a) {
         const int v = 2 * (u * kPrTB + t);
         const double rs = (sh[0][v] + sh[1][v]) + (sh[2][v] + sh[3][v]);
         const double as = (sh[0][v + 1] + sh[1][v + 1]) + (sh[2][v + 1] + sh[3][v + 1]);
-        const double nrm = kSqrt5 * sqrt(rs);
-        const double ex = exp(-nrm * a.inv_sig);
-        const double m = ex * a.k5;
+        const MaternRow mr = matern_row(rs, a.mc);
         // a row past the chunk's end contributes nothing
-        w[u][t] = rok[t] ? fma(a.sig, nrm, a.sig2) * m : 0.0;
-        c[u][t] = rok[t] ? 5.0 * m * as : 0.0;
+        w[u][t] = rok[t] ? mr.w : 0.0;
+        c[u][t] = rok[t] ? 5.0 * mr.m * as : 0.0;
         if (rok[t]) en[u] = fma(as, w[u][t], en[u]);
         if (ECSTR) {  // ej = 0 past the chunk's end (w = c = 0 there)
-          const double kee = fma(nrm * a.inv_sig, fma(nrm, a.inv_3sig, 1.0), 1.0) * ex;
+          const double kee = kee_of(mr.nrm, mr.ex, a.mc.inv_sig, a.inv_3sig);
           c[u][t] = fma(ej[t], w[u][t], c[u][t]);
           if (rok[t]) en[u] = fma(ej[t], kee, en[u]);
         }
@@ -386,43 +357,21 @@ __global__ __launch_bounds__(256) void k_pr_stream(PrArgs a) {
 }
 
 // Fd[q][e] = sum_s part[s][q][e] and E[q] = std sum_s part[s][q][ecol] + c: a workgroup per
-// (kPrSumE entries, query); chunk group g adds the chunks [S g / 16, S (g + 1) / 16) in chunk
-// order (batches of 8 predicated loads in flight), then the 16 group sums are added in group
-// order.  Entry D stands for the energy column.
+// (kSumE entries, query), summed by chunk_sum (sgdml_pair.h).  Entry D stands for the energy
+// column.
 __global__ __launch_bounds__(256) void k_pr_sum(const double *__restrict__ part, int64_t PS,
                                                 int64_t ecol, int64_t D, int64_t nq, int S,
                                                 double std, double cint, double *__restrict__ Fd,
                                                 double *__restrict__ E) {
-  __shared__ double sP[kPrSumG][kPrSumE];
-  const int el = threadIdx.x % kPrSumE, g = threadIdx.x / kPrSumE;
-  const int64_t e = (int64_t)blockIdx.x * kPrSumE + el;
-  const int64_t q = blockIdx.y;
+  const int64_t e = (int64_t)blockIdx.x * kSumE + threadIdx.x % kSumE, q = blockIdx.y;
   const int64_t col = e < D ? e : ecol;
   const bool ok = e <= D;
-  const int z0 = (int)(((int64_t)S * g) / kPrSumG), z1 = (int)(((int64_t)S * (g + 1)) / kPrSumG);
-  const int64_t zs = nq * PS;
-  const double *src = part + q * PS + col;
-  double sum = 0.0;
-  for (int z = z0; z < z1; z += 8) {
-    double t[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t[u] = (ok && z + u < z1) ? src[(int64_t)(z + u) * zs] : 0.0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) sum += t[u];
-  }
-  sP[g][el] = sum;
-  __syncthreads();
-  if (g != 0 || !ok) return;
-  double fsum = sP[0][el];
-  for (int h = 1; h < kPrSumG; ++h) fsum += sP[h][el];
+  const double fsum = chunk_sum(part + q * PS + col, nq * PS, S, ok);
+  if (threadIdx.x >= kSumE || !ok) return;
   if (e < D)
     Fd[q * D + e] = fsum;
   else
     E[q] = __dadd_rn(__dmul_rn(fsum, std), cint);  // E_F *= std; E = E_F[:, 0] + c
-}
-
-__device__ __forceinline__ int64_t pr_pairidx(int a, int b) {
-  return a > b ? (int64_t)a * (a - 1) / 2 + b : (int64_t)b * (b - 1) / 2 + a;
 }
 
 // F[q][3 at + c] = std sum_b (+-) Rdd_q[pair(at, b)][c] Fd_q[pair(at, b)], partners b in
@@ -445,7 +394,7 @@ __global__ __launch_bounds__(64) void k_pr_jt(const double *__restrict__ Rdd,
     for (int u = 0; u < 8; ++u) {
       const int b = b0 + u;
       const bool ok = b < n && b != at;
-      const int64_t d = ok ? pr_pairidx(at, b) : 0;
+      const int64_t d = ok ? pair_idx(at, b) : 0;
       const double v = ok ? jr[d * 3] : 0.0;
       rv[u] = at > b ? -v : v;
       fv[u] = ok ? fr[d] : 0.0;
@@ -478,15 +427,6 @@ const PrVariant *pr_variant(int64_t D) {
   for (const PrVariant &v : kPrVariants)
     if (D <= (int64_t)v.L * v.DL) return &v;
   return nullptr;
-}
-
-template <typename T>
-int pr_alloc(mlff_ctx *ctx, T **p, int64_t count) {
-  if (hipMalloc(p, sizeof(T) * (size_t)std::max<int64_t>(count, 1)) != hipSuccess) {
-    *p = nullptr;
-    return set_error(ctx, MLFF_ERR_NOMEM, "predict: device allocation failed");
-  }
-  return MLFF_OK;
 }
 
 }  // namespace
@@ -574,15 +514,12 @@ int pred_set_model(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc_a
     pred_free(ctx->pred);
     return rc;
   };
-  int rc;
-  if ((rc = pr_alloc(ctx, &pd.Rt, MP * D)) != MLFF_OK) return fail(rc);
-  if ((rc = pr_alloc(ctx, &pd.Zt, MP * D)) != MLFF_OK) return fail(rc);
-  if ((rc = pr_alloc(ctx, &pd.Rq, slab * 3 * n)) != MLFF_OK) return fail(rc);
-  if ((rc = pr_alloc(ctx, &pd.Rdq, slab * D)) != MLFF_OK) return fail(rc);
-  if ((rc = pr_alloc(ctx, &pd.Rddq, slab * D * 3)) != MLFF_OK) return fail(rc);
-  if ((rc = pr_alloc(ctx, &pd.part, (int64_t)pd.S * slab * pd.PS)) != MLFF_OK) return fail(rc);
-  if ((rc = pr_alloc(ctx, &pd.Fd, slab * D)) != MLFF_OK) return fail(rc);
-  if ((rc = pr_alloc(ctx, &pd.EF, slab * (3 * n + 1))) != MLFF_OK) return fail(rc);
+  const std::pair<double **, int64_t> bufs[] = {
+      {&pd.Rt, MP * D},         {&pd.Zt, MP * D},           {&pd.Rq, slab * 3 * n},
+      {&pd.Rdq, slab * D},      {&pd.Rddq, slab * D * 3},   {&pd.part, (int64_t)pd.S * slab * pd.PS},
+      {&pd.Fd, slab * D},       {&pd.EF, slab * (3 * n + 1)}};
+  for (const auto &b : bufs)
+    if (const int rc = dev_alloc(ctx, b.first, b.second, "predict")) return fail(rc);
   if (hipHostMalloc(&pd.h_in, sizeof(double) * slab * 3 * n) != hipSuccess ||
       hipHostMalloc(&pd.h_out, sizeof(double) * slab * (3 * n + 1)) != hipSuccess)
     return fail(set_error(ctx, MLFF_ERR_NOMEM, "predict: pinned host allocation failed"));
@@ -605,7 +542,7 @@ int pred_set_energy_coefficients(mlff_ctx *ctx, const double *alphas_E) {
   std::vector<double> hE((size_t)pd.MP);
   for (int64_t j = 0; j < pd.M; ++j)
     for (int p = 0; p < pd.n_perms; ++p) hE[(size_t)(j * pd.n_perms + p)] = alphas_E[j];
-  if (pd.Et == nullptr) MLFF_TRY(pr_alloc(ctx, &pd.Et, pd.MP));
+  if (pd.Et == nullptr) MLFF_TRY(dev_alloc(ctx, &pd.Et, pd.MP, "predict"));
   if (hipMemcpy(pd.Et, hE.data(), sizeof(double) * pd.MP, hipMemcpyHostToDevice) != hipSuccess) {
     (void)hipFree(pd.Et);
     pd.Et = nullptr;
@@ -614,27 +551,30 @@ int pred_set_energy_coefficients(mlff_ctx *ctx, const double *alphas_E) {
   return MLFF_OK;
 }
 
+// the model part of the pair stage's arguments
+static PrArgs pr_model_args(const PredData &pd) {
+  PrArgs a{};
+  a.Rt = pd.Rt;
+  a.Zt = pd.Zt;
+  a.Et = pd.Et;
+  a.D = pd.D;
+  a.MP = pd.MP;
+  a.mc = matern_consts(pd.sig);
+  a.inv_3sig = 1.0 / (3.0 * pd.sig);
+  return a;
+}
+
 // descriptors of the nq queries in pd.Rq (Rdq, Rddq of the slab) and, with_fd, the pair stage
 // and the chunk sum (Fd of the slab)
 static void pr_launch_fd(const PredData &pd, int64_t nq, bool with_fd, hipStream_t s) {
   const int64_t D = pd.D;
-  PrArgs a;
+  PrArgs a = pr_model_args(pd);
   a.Rdq = pd.Rdq;
-  a.Rt = pd.Rt;
-  a.Zt = pd.Zt;
-  a.D = D;
   a.nq = nq;
-  a.MP = pd.MP;
   a.S = pd.S;
-  a.sig = pd.sig;
-  a.sig2 = pd.sig * pd.sig;
-  a.inv_sig = 1.0 / pd.sig;
-  a.k5 = 5.0 / (3.0 * pd.sig * pd.sig * pd.sig * pd.sig);
   a.part = pd.part;
   a.PS = pd.PS;
   a.ecol = pd.ecol;
-  a.Et = pd.Et;
-  a.inv_3sig = 1.0 / (3.0 * pd.sig);
   const bool ecstr = pd.Et != nullptr;
   const unsigned gx = (unsigned)std::min<int64_t>((D + 255) / 256, 64);
   hipLaunchKernelGGL(k_pr_desc, dim3(gx, (unsigned)nq), dim3(256), 0, s, pd.Rq, pd.n, pd.Rdq, pd.Rddq);
@@ -649,7 +589,7 @@ static void pr_launch_fd(const PredData &pd, int64_t nq, bool with_fd, hipStream
                        dim3((unsigned)((nq + kPrQB - 1) / kPrQB), (unsigned)pd.S), dim3(256), 0, s,
                        a);
   }
-  hipLaunchKernelGGL(k_pr_sum, dim3((unsigned)((D + 1 + kPrSumE - 1) / kPrSumE), (unsigned)nq),
+  hipLaunchKernelGGL(k_pr_sum, dim3((unsigned)((D + 1 + kSumE - 1) / kSumE), (unsigned)nq),
                      dim3(256), 0, s, pd.part, pd.PS, pd.ecol, D, nq, pd.S, pd.std, pd.c, pd.Fd, pd.EF);
 }
 

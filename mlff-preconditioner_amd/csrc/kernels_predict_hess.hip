@@ -27,7 +27,7 @@
 //      lane + 64, ..., then the shuffle tree) and lane 0 the row's scalars 5 m, beta + 5 m e and
 //      5 m a + e w;
 //   2. thread (row, t < 3n) sums p_t and s_t over the n - 1 partners in increasing partner order
-//      (as k_pr_jt) and writes p, u, t of the row to LDS;
+//      (k_pr_jt's order) and writes p, u, t of the row to LDS;
 //   3. thread (block, slot) adds the rows slot, slot + RS, ... of the step to its 16 accumulators:
 //      8 LDS reads of 16 bytes for 32 fmas.  RS = min(TB, 256 / blocks of the tile) row slots
 //      share a block when the tile has few blocks (ethanol: 28 blocks, 8 slots), so that a small
@@ -35,17 +35,22 @@
 // k_hs_pair_s<TB, ECSTR> (below) is the same stage for molecules whose rows fit LDS (up to 24
 // atoms), with the lanes of steps 1 and 2 on different rows; hs_staged_tb chooses between them.
 // Chunk partials part[s][q][PS] (the blocks, then sum 5 m a + e w, then Fd where the pair stage
-// forms it: D <= 512, else the prediction's pair stage runs first), k_hs_sum adds the
-// chunks in k_pr_sum's fixed order, k_hs_fin subtracts the scalar times J^T J, adds the
-// second-derivative term, scales by std and writes the full matrix: entry (i, k) and (k, i) are
-// the same expression of (max, min), so H equals its transpose bit for bit.
+// forms it: D <= 512, else the prediction's pair stage runs first), k_hs_sum adds the chunks with
+// chunk_sum (k_pr_sum's fixed order), k_hs_fin subtracts the scalar times J^T J, adds the second-
+// derivative term, scales by std and writes the full matrix: entry (i, k) and (k, i) are the same
+// expression of (max, min), so H equals its transpose bit for bit.
 //
 // Determinism: no atomics; the chunk count, the tiles, the row slots and every reduction order
 // depend on the model (M n_perms, n, constrained or not) only, and no sum runs across queries: a
 // query's Hessian has the same bits whatever the batch, its position in it, the slab size or the
 // device split.  The ECSTR terms enter as fma(5 m, e, beta) and fma(e, w, 5 m a): alphas_E = 0
 // gives the unconstrained model's bits.
+//
+// hess_row (the prediction's matern_m / matern_w, so the fused Fd has its bits), pair_idx and
+// chunk_sum are sgdml_pair.h's; the pair stages share hs_map.  "twin": the same text in both stages,
+// because as a function it changed their compiled code (profiles/sgdml_shared/README.txt).
 #include "common.h"
+#include "sgdml_pair.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -61,9 +66,6 @@ constexpr int kHsMaxChunks = 256;
 constexpr int kHsTB = 8;           // rows per step while 3 TB N3P doubles fit 48 KB of LDS
 constexpr int kHsMaxN3P = 2048;    // TB = 1: 3 N3P doubles within 48 KB
 constexpr int kHsFdU = 2;          // Fd entries per thread of the fused form: D <= 512
-constexpr int kHsSumE = 16;        // k_hs_sum: entries per workgroup
-constexpr int kHsSumG = 16;        // k_hs_sum: chunk groups
-constexpr double kSqrt5 = 2.23606797749978969640917366873127623544;
 
 struct HsArgs {
   const double *Rdq;   // nq x D
@@ -73,13 +75,17 @@ struct HsArgs {
   int S;               // chunks (gridDim.y)
   int n, N3, N3P;      // atoms, 3 n, 3 n rounded up to 4
   int nblk;            // 4 x 4 blocks of the lower triangle
-  double sig, sig2, inv_sig, k5;
+  MaternConsts mc;     // sgdml_pair.h
   double *part;        // S x nq x PS
   int64_t PS;          // 16 nblk + 2 (the blocks, the scalar, padding), + D rounded up to 2 with FD
 };
 
-__device__ __forceinline__ int64_t hs_pairidx(int a, int b) {
-  return a > b ? (int64_t)a * (a - 1) / 2 + b : (int64_t)b * (b - 1) / 2 + a;
+// both pair stages: tile `tile` holds the blocks [b0, b0 + nbt), RS row slots share a block
+struct HsMap { int b0, nbt, RS, blk, slot; };
+__device__ __forceinline__ HsMap hs_map(int TB, int nblk, int tile, int tid) {
+  const int b0 = tile * 256;
+  const int nbt = min(256, nblk - b0);
+  return {b0, nbt, min(TB, 256 / nbt), tid % nbt, tid / nbt};
 }
 
 // FD: the workgroups of tile 0 also accumulate the chunk's Fd = sum (5 m a + e w) diff - w z
@@ -96,13 +102,11 @@ __global__ __launch_bounds__(kHsThreads) void k_hs_pair(HsArgs a) {
   // the padding entries [N3, N3P) of every row stay zero
   for (int e = tid; e < 3 * TB * N3P; e += kHsThreads) lds[e] = 0.0;
   // this thread's block of the tile and its row slot
-  const int b0 = (int)blockIdx.z * 256;
-  const int nbt = min(256, a.nblk - b0);
-  const int RS = min(TB, 256 / nbt);
-  const int blk = tid % nbt, slot = tid / nbt;
+  const HsMap hm = hs_map(TB, a.nblk, (int)blockIdx.z, tid);
+  const int b0 = hm.b0, nbt = hm.nbt, RS = hm.RS, blk = hm.blk, slot = hm.slot;
   const bool act = slot < RS;
   int bi, bk;
-  {
+  {  // twin (k_hs_pair / k_hs_pair_s): B = bi (bi + 1) / 2 + bk inverted, the sqrt estimate corrected
     const int B = b0 + blk;
     bi = (int)((sqrt(8.0 * (double)B + 1.0) - 1.0) * 0.5);
     while (bi * (bi + 1) / 2 > B) --bi;
@@ -134,21 +138,12 @@ __global__ __launch_bounds__(kHsThreads) void k_hs_pair(HsArgs a) {
       r2 = wave_sum(r2);
       aa = wave_sum(aa);
       if (lane == 0) {
-        const double nrm = kSqrt5 * sqrt(r2);
-        const double m = exp(-nrm * a.inv_sig) * a.k5;
-        const double m5 = 5.0 * m;
-        double cdd = nrm > 0.0 ? 5.0 * m5 * aa / (a.sig * nrm) : 0.0;
-        double ci = m5 * aa;
-        const double w = fma(a.sig, nrm, a.sig2) * m;
-        if (ECSTR) {
-          const double ej = a.Et[j0 + r];
-          cdd = fma(m5, ej, cdd);
-          ci = fma(ej, w, ci);
-        }
-        sc5m[r] = m5;
-        scdd[r] = cdd;
-        sci[r] = ci;
-        if (FD) scw[r] = w;
+        HessRow hr = hess_row(r2, aa, a.mc);
+        if (ECSTR) hr = hess_row_ecstr(hr, a.Et[j0 + r]);
+        sc5m[r] = hr.m5;
+        scdd[r] = hr.cdd;
+        sci[r] = hr.ci;
+        if (FD) scw[r] = hr.w;
       }
     }
     __syncthreads();  // the scalars are written; the previous step's p, u, t are consumed
@@ -172,7 +167,7 @@ __global__ __launch_bounds__(kHsThreads) void k_hs_pair(HsArgs a) {
 #pragma unroll 4
       for (int b = 0; b < n; ++b) {
         if (b == at) continue;
-        const int64_t d = hs_pairidx(at, b);
+        const int64_t d = pair_idx(at, b);
         const double v = jq[d * 3 + c];
         const double jv = at > b ? -v : v;
         pp = fma(jv, rd[d] - rt[d], pp);
@@ -186,7 +181,7 @@ __global__ __launch_bounds__(kHsThreads) void k_hs_pair(HsArgs a) {
     __syncthreads();
     // 3. H_ik += p_i u_k + t_i p_k on this thread's block, the rows of its slot
     if (act) {
-      for (int r = slot; r < cnt; r += RS) {
+      for (int r = slot; r < cnt; r += RS) {  // twin (k_hs_pair / k_hs_pair_s): the 4 x 4 update
         const double2 *pi = reinterpret_cast<const double2 *>(sp + r * N3P + 4 * bi);
         const double2 *ti = reinterpret_cast<const double2 *>(st + r * N3P + 4 * bi);
         const double2 *uk = reinterpret_cast<const double2 *>(su + r * N3P + 4 * bk);
@@ -207,7 +202,7 @@ __global__ __launch_bounds__(kHsThreads) void k_hs_pair(HsArgs a) {
     __syncthreads();  // thread 0 has read this step's scalars: the next step writes them
   }
   double *out = a.part + (s * a.nq + q) * a.PS;
-  if (RS > 1) {
+  if (RS > 1) {  // twin (k_hs_pair / k_hs_pair_s): the slot merge and the store of the block
     // the slots of a block in slot order (lds is free: the loop ends with a barrier)
     if (act) {
 #pragma unroll
@@ -230,7 +225,7 @@ __global__ __launch_bounds__(kHsThreads) void k_hs_pair(HsArgs a) {
   }
   if (blockIdx.z != 0) return;
   const int64_t c0 = 16 * (int64_t)a.nblk;
-  if (tid == 0) {
+  if (tid == 0) {  // twin (k_hs_pair / k_hs_pair_s): the scalar, the padding and Fd
     out[c0] = scal;
     out[c0 + 1] = 0.0;                               // padding: k_hs_sum adds whole rows
     if (FD && (D & 1)) out[c0 + 2 + D] = 0.0;
@@ -272,13 +267,11 @@ __global__ __launch_bounds__(kHsThreads) void k_hs_pair_s(HsArgs a) {
   for (int e = tid; e < 3 * TB * N3P; e += kHsThreads) lds[e] = 0.0;
   // the query's compact Jacobian, read by every thread of D. in every step
   for (int e = tid; e < 3 * D; e += kHsThreads) sj[e] = a.Rddq[q * (int64_t)D * 3 + e];
-  const int b0 = (int)blockIdx.z * 256;
-  const int nbt = min(256, a.nblk - b0);
-  const int RS = min(TB, 256 / nbt);
-  const int blk = tid % nbt, slot = tid / nbt;
+  const HsMap hm = hs_map(TB, a.nblk, (int)blockIdx.z, tid);
+  const int b0 = hm.b0, nbt = hm.nbt, RS = hm.RS, blk = hm.blk, slot = hm.slot;
   const bool act = slot < RS;
   int bi, bk;
-  {
+  {  // twin (k_hs_pair / k_hs_pair_s): B = bi (bi + 1) / 2 + bk inverted, the sqrt estimate corrected
     const int B = b0 + blk;
     bi = (int)((sqrt(8.0 * (double)B + 1.0) - 1.0) * 0.5);
     while (bi * (bi + 1) / 2 > B) --bi;
@@ -336,22 +329,13 @@ __global__ __launch_bounds__(kHsThreads) void k_hs_pair_s(HsArgs a) {
         r2 += spart[0][h * TB + tid];
         aa += spart[1][h * TB + tid];
       }
-      const double nrm = kSqrt5 * sqrt(r2);
-      const double m = exp(-nrm * a.inv_sig) * a.k5;
-      const double m5 = 5.0 * m;
-      double cdd = nrm > 0.0 ? 5.0 * m5 * aa / (a.sig * nrm) : 0.0;
-      double ci = m5 * aa;
-      const double w = fma(a.sig, nrm, a.sig2) * m;
-      if (ECSTR) {
-        const double ej = a.Et[j0 + tid];
-        cdd = fma(m5, ej, cdd);
-        ci = fma(ej, w, ci);
-      }
-      sc5m[tid] = m5;
-      scdd[tid] = cdd;
-      sci[tid] = ci;
-      scw[tid] = w;
-      scal += ci;  // row tid of every step; the TB partial sums meet in row order at the end
+      HessRow hr = hess_row(r2, aa, a.mc);
+      if (ECSTR) hr = hess_row_ecstr(hr, a.Et[j0 + tid]);
+      sc5m[tid] = hr.m5;
+      scdd[tid] = hr.cdd;
+      sci[tid] = hr.ci;
+      scw[tid] = hr.w;
+      scal += hr.ci;  // row tid of every step; the TB partial sums meet in row order at the end
     }
     __syncthreads();
     // D.
@@ -373,6 +357,7 @@ __global__ __launch_bounds__(kHsThreads) void k_hs_pair_s(HsArgs a) {
 #pragma unroll 4
       for (int b = 0; b < n; ++b) {
         if (b == at) continue;
+        // twin of pair_idx (sgdml_pair.h) in 32-bit arithmetic (D <= 512 here)
         const int d = at > b ? at * (at - 1) / 2 + b : b * (b - 1) / 2 + at;
         const double v = sj[d * 3 + c];
         const double jv = at > b ? -v : v;
@@ -387,7 +372,7 @@ __global__ __launch_bounds__(kHsThreads) void k_hs_pair_s(HsArgs a) {
     __syncthreads();
     // E. H_ik += p_i u_k + t_i p_k on this thread's block, the rows of its slot
     if (act) {
-      for (int r = slot; r < cnt; r += RS) {
+      for (int r = slot; r < cnt; r += RS) {  // twin (k_hs_pair / k_hs_pair_s): the 4 x 4 update
         const double2 *pi = reinterpret_cast<const double2 *>(sp + r * N3P + 4 * bi);
         const double2 *ti = reinterpret_cast<const double2 *>(st + r * N3P + 4 * bi);
         const double2 *uk = reinterpret_cast<const double2 *>(su + r * N3P + 4 * bk);
@@ -409,7 +394,7 @@ __global__ __launch_bounds__(kHsThreads) void k_hs_pair_s(HsArgs a) {
   double *out = a.part + (s * a.nq + q) * a.PS;
   __syncthreads();  // every thread is through with the last step: lds and spart are free
   if (tid < TB) spart[0][tid] = scal;
-  if (RS > 1) {
+  if (RS > 1) {  // twin (k_hs_pair / k_hs_pair_s): the slot merge and the store of the block
     if (act) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) lds[(slot * nbt + blk) * 16 + e] = acc[e];
@@ -432,7 +417,7 @@ __global__ __launch_bounds__(kHsThreads) void k_hs_pair_s(HsArgs a) {
   if (blockIdx.z != 0) return;
   const int64_t c0 = 16 * (int64_t)a.nblk;
   if (RS <= 1) __syncthreads();  // spart (the slots' barrier above serves otherwise)
-  if (tid == 0) {
+  if (tid == 0) {  // twin (k_hs_pair / k_hs_pair_s): the scalar, the padding and Fd
     double v = spart[0][0];
     for (int r = 1; r < TB; ++r) v += spart[0][r];
     out[c0] = v;
@@ -446,31 +431,13 @@ __global__ __launch_bounds__(kHsThreads) void k_hs_pair_s(HsArgs a) {
   }
 }
 
-// sum[q][e] = sum_s part[s][q][e], e < PS: k_pr_sum's order (16 groups of consecutive chunks in
-// chunk order, batches of 8 loads in flight, then the groups in order)
+// sum[q][e] = sum_s part[s][q][e], e < PS: chunk_sum (sgdml_pair.h), the order of k_pr_sum
 __global__ __launch_bounds__(256) void k_hs_sum(const double *__restrict__ part, int64_t PS, int64_t nq,
                                                 int S, double *__restrict__ sum) {
-  __shared__ double sP[kHsSumG][kHsSumE];
-  const int el = threadIdx.x % kHsSumE, g = threadIdx.x / kHsSumE;
-  const int64_t e = (int64_t)blockIdx.x * kHsSumE + el;
-  const int64_t q = blockIdx.y;
+  const int64_t e = (int64_t)blockIdx.x * kSumE + threadIdx.x % kSumE, q = blockIdx.y;
   const bool ok = e < PS;
-  const int z0 = (int)(((int64_t)S * g) / kHsSumG), z1 = (int)(((int64_t)S * (g + 1)) / kHsSumG);
-  const int64_t zs = nq * PS;
-  const double *src = part + q * PS + (ok ? e : 0);
-  double acc = 0.0;
-  for (int z = z0; z < z1; z += 8) {
-    double t[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) t[u] = (ok && z + u < z1) ? src[(int64_t)(z + u) * zs] : 0.0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc += t[u];
-  }
-  sP[g][el] = acc;
-  __syncthreads();
-  if (g != 0 || !ok) return;
-  double fsum = sP[0][el];
-  for (int h = 1; h < kHsSumG; ++h) fsum += sP[h][el];
+  const double fsum = chunk_sum(part + q * PS + (ok ? e : 0), nq * PS, S, ok);
+  if (threadIdx.x >= kSumE || !ok) return;
   sum[q * PS + e] = fsum;
 }
 
@@ -498,7 +465,7 @@ __global__ __launch_bounds__(256) void k_hs_fin(const double *__restrict__ sum, 
   const double *rd = Rd + q * D, *jr = Rdd + q * D * 3, *fd = Fd + q * fds;  // row stride of Fd
   double val;
   if (A != B) {
-    const int64_t d = hs_pairidx(A, B);
+    const int64_t d = pair_idx(A, B);
     const double xy = jr[d * 3 + cI] * jr[d * 3 + cK];
     const double r1 = rd[d];
     double bm = 3.0 * xy / r1;
@@ -509,7 +476,7 @@ __global__ __launch_bounds__(256) void k_hs_fin(const double *__restrict__ sum, 
     double jtj = 0.0, d2 = 0.0;
     for (int b = 0; b < n; ++b) {
       if (b == A) continue;
-      const int64_t d = hs_pairidx(A, b);
+      const int64_t d = pair_idx(A, b);
       const double xy = jr[d * 3 + cI] * jr[d * 3 + cK];
       const double r1 = rd[d];
       double bm = 3.0 * xy / r1;
@@ -520,15 +487,6 @@ __global__ __launch_bounds__(256) void k_hs_fin(const double *__restrict__ sum, 
     val = fma(-scal, jtj, hs) + d2;
   }
   H[q * N3 * N3 + e] = std * val;
-}
-
-template <typename T>
-int hs_alloc(mlff_ctx *ctx, T **p, int64_t count) {
-  if (hipMalloc(p, sizeof(T) * (size_t)std::max<int64_t>(count, 1)) != hipSuccess) {
-    *p = nullptr;
-    return set_error(ctx, MLFF_ERR_NOMEM, "predict hessian: device allocation failed");
-  }
-  return MLFF_OK;
 }
 
 // the pair stage forms Fd itself while kHsFdU entries per thread cover D; above, the
@@ -568,9 +526,9 @@ int hs_prepare(mlff_ctx *ctx) {
   slab = std::max<int64_t>(1, std::min<int64_t>(slab, pd.slab));
   pd.hs_slab = slab;
   int rc;
-  if ((rc = hs_alloc(ctx, &pd.hs_part, (int64_t)pd.hs_S * slab * PS)) != MLFF_OK ||
-      (rc = hs_alloc(ctx, &pd.hs_sum, slab * PS)) != MLFF_OK ||
-      (rc = hs_alloc(ctx, &pd.hs_H, slab * N3 * N3)) != MLFF_OK) {
+  if ((rc = dev_alloc(ctx, &pd.hs_part, (int64_t)pd.hs_S * slab * PS, "predict hessian")) != MLFF_OK ||
+      (rc = dev_alloc(ctx, &pd.hs_sum, slab * PS, "predict hessian")) != MLFF_OK ||
+      (rc = dev_alloc(ctx, &pd.hs_H, slab * N3 * N3, "predict hessian")) != MLFF_OK) {
     pred_hess_free(pd);
     return rc;
   }
@@ -584,6 +542,22 @@ int hs_prepare(mlff_ctx *ctx) {
 }
 
 using HsFn = void (*)(HsArgs);
+
+// the model part of the pair stage's arguments (after hs_prepare)
+HsArgs hs_model_args(const PredData &pd) {
+  HsArgs a{};
+  a.Rt = pd.Rt;
+  a.Zt = pd.Zt;
+  a.Et = pd.Et;
+  a.D = pd.D;
+  a.MP = pd.MP;
+  a.n = pd.n;
+  a.N3 = 3 * pd.n;
+  a.N3P = hs_n3p(pd.n);
+  a.nblk = (int)pd.hs_nblk;
+  a.mc = matern_consts(pd.sig);
+  return a;
+}
 
 }  // namespace
 
@@ -600,23 +574,10 @@ int pred_hess_run(mlff_ctx *ctx, const double *R, int64_t Q, double *H_out) {
   const PredData &pd = ctx->pred;
   hipStream_t s = ctx->stream;
   const int64_t N3 = 3 * (int64_t)pd.n, D = pd.D;
-  HsArgs a;
+  HsArgs a = hs_model_args(pd);
   a.Rdq = pd.Rdq;
   a.Rddq = pd.Rddq;
-  a.Rt = pd.Rt;
-  a.Zt = pd.Zt;
-  a.Et = pd.Et;
-  a.D = D;
-  a.MP = pd.MP;
   a.S = pd.hs_S;
-  a.n = pd.n;
-  a.N3 = (int)N3;
-  a.N3P = hs_n3p(pd.n);
-  a.nblk = (int)pd.hs_nblk;
-  a.sig = pd.sig;
-  a.sig2 = pd.sig * pd.sig;
-  a.inv_sig = 1.0 / pd.sig;
-  a.k5 = 5.0 / (3.0 * pd.sig * pd.sig * pd.sig * pd.sig);
   a.part = pd.hs_part;
   a.PS = pd.hs_PS;
   const bool ecstr = pd.Et != nullptr;
@@ -645,7 +606,7 @@ int pred_hess_run(mlff_ctx *ctx, const double *R, int64_t Q, double *H_out) {
     a.nq = nq;
     MLFF_TRY(pred_fd_slab(ctx, R + q0 * N3, nq, !pd.hs_fd));
     hipLaunchKernelGGL(fn, dim3((unsigned)nq, (unsigned)pd.hs_S, ntile), dim3(kHsThreads), lds, s, a);
-    hipLaunchKernelGGL(k_hs_sum, dim3((unsigned)((a.PS + kHsSumE - 1) / kHsSumE), (unsigned)nq), dim3(256),
+    hipLaunchKernelGGL(k_hs_sum, dim3((unsigned)((a.PS + kSumE - 1) / kSumE), (unsigned)nq), dim3(256),
                        0, s, pd.hs_part, a.PS, nq, pd.hs_S, pd.hs_sum);
     hipLaunchKernelGGL(k_hs_fin, dim3((unsigned)((N3 * N3 + 255) / 256), (unsigned)nq), dim3(256), 0, s,
                        pd.hs_sum, a.PS, pd.Rdq, pd.Rddq, pd.hs_fd ? pd.hs_sum + c0 + 2 : pd.Fd,

@@ -25,10 +25,11 @@
 // chunks split the (j, p) range so that the grid fills the chip.
 // k_pt_fin: F_i = sum_s part[s][i] (fixed chunk order), y rows = J_i^T F_i (partners b in
 // increasing order), y = sigma y + lam x, and the x . y partials of the PCG step.
-// Rounding: another summation order of the reference's products.
+// Rounding: another summation order of the reference's products; sgdml_pair.h.
 // The force sum stays on the fp64 vector pipe: on MI355X the fp64 matrix pipe is the slower one
 // (DESIGN.md 3.8).
 #include "common.h"
+#include "sgdml_pair.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -38,7 +39,6 @@ namespace mlff {
 namespace {
 
 constexpr int kPtThreads = 256;
-constexpr double kSqrt5 = 2.23606797749978969640917366873127623544;
 
 struct PtArgs {
   const double *Rd;  // M x D, query rows i0 + il
@@ -46,7 +46,7 @@ struct PtArgs {
   const double *Zt;  // MP x D
   int64_t D, i0, ni, MP;
   int S;             // chunks of the (j, p) range (gridDim.y)
-  double sig, sig2, inv_sig, k5;  // k5 = 5 / (3 sig^4)
+  MaternConsts mc;   // sgdml_pair.h
   double *part;      // S x ni x DP
 };
 
@@ -155,10 +155,9 @@ void k_pt_pair(PtArgs a, const int *__restrict__ status) {
 #pragma unroll
       for (int q = 0; q < NJ; ++q) {
         const double rs = group_sum<L>(r2[q]), as = group_sum<L>(ad[q]);
-        const double nrm = kSqrt5 * sqrt(rs);
-        const double m = exp(-nrm * a.inv_sig) * a.k5;
-        w[q] = fma(a.sig, nrm, a.sig2) * m;
-        c[q] = 5.0 * m * as;
+        const MaternRow mr = matern_row(rs, a.mc);
+        w[q] = mr.w;
+        c[q] = 5.0 * mr.m * as;
       }
       // the second pass re-reads what it does not keep (no CSE of the LDS loads across this)
       if (!KEEP_DF || !KEEP_Z) asm volatile("" ::: "memory");
@@ -196,10 +195,6 @@ void k_pt_pair(PtArgs a, const int *__restrict__ status) {
 #pragma unroll
   for (int e = 0; e < DL / 2; ++e)
     *reinterpret_cast<double2 *>(out + 2 * (l + L * e)) = make_double2(f[2 * e], f[2 * e + 1]);
-}
-
-__device__ __forceinline__ int64_t pt_pair(int a, int b) {
-  return a > b ? (int64_t)a * (a - 1) / 2 + b : (int64_t)b * (b - 1) / 2 + a;
 }
 
 struct PtFin {
@@ -290,7 +285,7 @@ __global__ __launch_bounds__(256) void k_pt_fin(PtFin a, const int *__restrict__
       double acc = 0.0;
       for (int b = 0; b < a.n; ++b) {
         if (b == at) continue;
-        const int64_t d = pt_pair(at, b);
+        const int64_t d = pair_idx(at, b);
         const double rv = sR[d * 3 + c];
         acc = fma(at > b ? -rv : rv, sF[d], acc);
       }
@@ -402,10 +397,7 @@ void launch_pt_operator(const MfData &mf, const double *Rt, const double *xc, in
   a.ni = mf.ni;
   a.MP = MP;
   a.S = mf.pt_S;
-  a.sig = mf.sig;
-  a.sig2 = mf.sig * mf.sig;
-  a.inv_sig = 1.0 / mf.sig;
-  a.k5 = 5.0 / (3.0 * mf.sig * mf.sig * mf.sig * mf.sig);
+  a.mc = matern_consts(mf.sig);
   a.part = mf.ptpart;
   const int64_t G = v->G;
   hipLaunchKernelGGL(v->fn, dim3((unsigned)((mf.ni + G - 1) / G), (unsigned)mf.pt_S), dim3(kPtThreads),

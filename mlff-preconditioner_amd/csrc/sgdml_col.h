@@ -1,19 +1,12 @@
-// Device helpers shared by the sGDML kernels of kernels_gen.hip and the persistent pivoted
-// Cholesky of kernels_pivchol.hip: the descriptor-pair index / Jacobian sign and one wave's
-// rows of a single operator column (the body of k_sgdml_col, so both produce the same bits).
+// Device helper shared by the sGDML kernels of kernels_gen.hip and the persistent pivoted
+// Cholesky of kernels_pivchol.hip: one wave's rows of a single operator column (the body of
+// k_sgdml_col, so both produce the same bits).  pair_idx / pair_sign: sgdml_pair.h.
 #pragma once
 
 #include "common.h"
+#include "sgdml_pair.h"
 
 namespace mlff {
-
-__device__ __forceinline__ int64_t pair_idx(int a, int b) {
-  // tril_indices(n, -1) ordering, a != b
-  return a > b ? (int64_t)a * (a - 1) / 2 + b : (int64_t)b * (b - 1) / 2 + a;
-}
-__device__ __forceinline__ double pair_sign(int a, int b) {  // sign of J[pair(a,b), atom a]
-  return a > b ? -1.0 : 1.0;
-}
 
 constexpr int kColRows = 64;
 

@@ -1,8 +1,12 @@
-"""Dump the predictor's E, F for cases of tests/golden/sgdml_predict_cases.npz, so that two
-builds can be compared bit for bit:
+"""Dump the predictor's E, F (and Hessians) for cases of tests/golden/sgdml_predict_cases.npz, so
+that two builds can be compared bit for bit:
 
     python tools/dump_predict.py --out a.npz [--tree /path/to/another/checkout] [--cases eth3 eth tube]
+                                 [--hessian] [--energy-constraints]
     python tools/dump_predict.py --compare a.npz b.npz
+
+--hessian also stores gd.hessian(R) of every case.  --energy-constraints gives every model a
+deterministic alphas_E (M standard normal draws, seed 20240), so that the ECSTR kernels run.
 
 --tree: import sgdml_amd (and its libmlffpcg.so) from that checkout instead of this one; the
 cases are always read from this one.  Default forms (tile for D <= 288, stream otherwise).
@@ -19,7 +23,10 @@ import numpy as np
 REPO = Path(__file__).resolve().parent.parent
 
 
-def dump(tree: Path, names, out: Path):
+ALPHAS_E_SEED = 20240
+
+
+def dump(tree: Path, names, out: Path, hessian: bool = False, energy_constraints: bool = False):
     sys.path[:0] = [str(tree / "mlff-preconditioner_amd")]
     import sgdml_amd
     from sgdml_amd import _native
@@ -34,9 +41,15 @@ def dump(tree: Path, names, out: Path):
         Rd, Rdd = host_descriptors(g("R_train"))
         model = {"type": "m", "z": g("z"), "perms": g("perms"), "sig": g("sig"), "std": g("std"),
                  "c": g("c"), "R_desc": Rd.T, "R_d_desc_alpha": r_d_desc_alpha(Rdd, g("alphas_F"))}
+        if energy_constraints:
+            M = g("R_train").shape[0]
+            model["alphas_E"] = np.random.default_rng(ALPHAS_E_SEED).standard_normal(M)
         with sgdml_amd.GDMLPredict(model, device=0) as gd:
             E, F = gd.predict(g("R"))
-            print(f"{name}: form {gd.form}, Q = {E.size}, build {_native.build_hash()}", flush=True)
+            print(f"{name}: form {gd.form}, Q = {E.size}, use_E_cstr {gd.use_E_cstr}, "
+                  f"build {_native.build_hash()}", flush=True)
+            if hessian:
+                res[f"{name}__H"] = gd.hessian(g("R"))
         res[f"{name}__E"], res[f"{name}__F"] = E, F
     out.parent.mkdir(parents=True, exist_ok=True)
     np.savez(out, **res)
@@ -60,13 +73,15 @@ def main():
     ap.add_argument("--out", type=Path)
     ap.add_argument("--tree", type=Path, default=REPO)
     ap.add_argument("--cases", nargs="*", default=["eth3", "eth", "tube"])
+    ap.add_argument("--hessian", action="store_true")
+    ap.add_argument("--energy-constraints", action="store_true")
     ap.add_argument("--compare", nargs=2, type=Path)
     a = ap.parse_args()
     if a.compare:
         raise SystemExit(compare(*a.compare))
     if a.out is None:
         ap.error("--out or --compare is required")
-    dump(a.tree, a.cases, a.out)
+    dump(a.tree, a.cases, a.out, a.hessian, a.energy_constraints)
 
 
 if __name__ == "__main__":
