@@ -445,6 +445,11 @@ int mlff_timing_read_comm(mlff_ctx *ctx, double *ms, int64_t *count);
 int mlff_timing_reset(mlff_ctx *ctx);
 /* free / total bytes of the context's device (hipMemGetInfo) */
 int mlff_device_memory(mlff_ctx *ctx, int64_t *free_out, int64_t *total_out);
+/* bytes of device and pinned host memory the library's contexts and calls of this process hold
+ * right now (its own count, touched when it allocates and frees; unlike hipMemGetInfo it does
+ * not move with other processes' work on a shared device).  A context that is destroyed, a
+ * model or operator that is replaced and a call that returns give back exactly what they took. */
+int mlff_live_bytes(int64_t *bytes_out);
 
 #ifdef __cplusplus
 }

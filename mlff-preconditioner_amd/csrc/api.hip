@@ -67,7 +67,6 @@ ScratchScope::~ScratchScope() {
   const bool keep_first = !ch.empty() && ch[0].size == kScratchChunk;
   if (ch.size() > (keep_first ? 1u : 0u)) {
     (void)hipStreamSynchronize(ctx->stream);
-    for (size_t i = keep_first ? 1 : 0; i < ch.size(); ++i) (void)hipFree(ch[i].p);
     ch.resize(keep_first ? 1 : 0);
   }
   ctx->scratch_cur = 0;
@@ -90,9 +89,9 @@ int scratch_get(mlff_ctx *ctx, size_t bytes, void **out) {
       ctx->scratch_off = 0;
       continue;
     }
-    void *p = nullptr;
-    MLFF_HIP(ctx, hipMalloc(&p, std::max(bytes, kChunk)));
-    ch.push_back({static_cast<char *>(p), std::max(bytes, kChunk)});
+    DevBuf<char> p;
+    MLFF_HIP(ctx, p.alloc((int64_t)std::max(bytes, kChunk)));
+    ch.push_back({std::move(p), std::max(bytes, kChunk)});
     ctx->scratch_cur = ch.size() - 1;
     ctx->scratch_off = 0;
   }
@@ -287,19 +286,11 @@ namespace {
 constexpr int kTimingPool = 4096;
 
 int ensure_matrix(mlff_ctx *ctx) {
-  if (ctx->K == nullptr) {
-    MLFF_HIP(ctx, hipMalloc(&ctx->K, sizeof(double) * ctx->blk * ctx->ld));
-  }
-  return MLFF_OK;
-}
-
-int dev_free(void *p) {
-  if (p != nullptr) (void)hipFree(p);
+  if (ctx->K == nullptr) MLFF_HIP(ctx, ctx->K.alloc(ctx->blk * ctx->ld));
   return MLFF_OK;
 }
 
 void rbf_free(mlff_ctx *ctx) {
-  dev_free(ctx->rbf.Xs);
   ctx->rbf = RbfData();
   ctx->sym.gen = false;  // tiles generated from these points stay valid, but are only streamed
   ctx->sym.gsrc = SymGen{};
@@ -368,32 +359,21 @@ double *pq_part(mlff_ctx *c) { return c->part + 1 * kMaxPart; }
 double *rr_part(mlff_ctx *c) { return c->part + 2 * kMaxPart; }
 
 int alloc_panel(mlff_ctx *ctx, int64_t k) {
-  if (ctx->T != nullptr) {
-    (void)hipFree(ctx->T);
-    ctx->T = nullptr;
-  }
-  if (ctx->tpart_base != nullptr) {
-    (void)hipFree(ctx->tpart_base);
-    ctx->tpart_base = nullptr;
-    ctx->tpart = nullptr;
-  }
+  ctx->tpart_base.reset();
+  ctx->tpart = nullptr;
   ctx->spec_t = false;
-  MLFF_HIP(ctx, hipMalloc(&ctx->T, sizeof(double) * round_up(k, 8) * ctx->blk));
+  MLFF_HIP(ctx, ctx->T.alloc(round_up(k, 8) * ctx->blk));
   MLFF_HIP(ctx, hipMemsetAsync(ctx->T, 0, sizeof(double) * round_up(k, 8) * ctx->blk, ctx->stream));
   ctx->tsplit = choose_tsplit(k, ctx->blk);
   if (const char *e = std::getenv("MLFF_TSPLIT")) ctx->tsplit = std::max(1, std::atoi(e));  // sweeps
   // [rr partials (kVecGrid) | tpart (k x tsplit)]: on several ranks the end-of-iteration
   // ||r||^2 reduction and the next iteration's T r reduction share one all-reduce
-  MLFF_HIP(ctx, hipMalloc(&ctx->tpart_base, sizeof(double) * (kVecGrid + k * ctx->tsplit)));
+  MLFF_HIP(ctx, ctx->tpart_base.alloc(kVecGrid + k * ctx->tsplit));
   ctx->tpart = ctx->tpart_base + kVecGrid;
-  if (ctx->zpart != nullptr) {
-    (void)hipFree(ctx->zpart);
-    ctx->zpart = nullptr;
-  }
   ctx->zsplit = choose_zsplit(k, ctx->blk);
   if (const char *e = std::getenv("MLFF_ZSPLIT"))  // sweeps
     ctx->zsplit = (int)std::min<int64_t>(std::max(1, std::atoi(e)), (k + 15) / 16);
-  MLFF_HIP(ctx, hipMalloc(&ctx->zpart, sizeof(double) * ctx->zsplit * ctx->blk));
+  MLFF_HIP(ctx, ctx->zpart.alloc(ctx->zsplit * ctx->blk));
   // one rank, rows that fit a workgroup's registers: the one-pass apply (at >= 7 rows per
   // workgroup its G partial vectors are <= 2/7 of a panel pass) from k = 768, and at any k on
   // short rows (N_loc <= 4096), where the launches it saves dominate the step: ethanol M = 111
@@ -402,11 +382,9 @@ int alloc_panel(mlff_ctx *ctx, int64_t k) {
   // the same either way (52.3 / 52.0 us), and k = 554 keeps the two-pass order its golden
   // fixture's crossings were measured with (profiles/r05/lr_small/).  MLFF_LR_ROWS=0 / 1
   // forces the two-pass / one-pass apply (A/B, tests)
-  for (void **p : {(void **)&ctx->lr_zpart, (void **)&ctx->lr_slots, (void **)&ctx->lr_fault})
-    if (*p != nullptr) {
-      (void)hipFree(*p);
-      *p = nullptr;
-    }
+  ctx->lr_zpart.reset();
+  ctx->lr_slots.reset();
+  ctx->lr_fault.reset();
   const char *lr_env = std::getenv("MLFF_LR_ROWS");
   const bool lr_on = lr_env == nullptr || std::atoi(lr_env) != 0;
   ctx->lr_rows = ctx->world == 1 && lr_rows_fits(ctx->blk) &&
@@ -421,13 +399,13 @@ int alloc_panel(mlff_ctx *ctx, int64_t k) {
     ctx->lr_cluster = ctx->lr_q >= 1 && k >= 4 * (int64_t)ctx->lr_q;
   }
   if (ctx->lr_rows)
-    MLFF_HIP(ctx, hipMalloc(&ctx->lr_zpart, sizeof(double) * lr_rows_groups(k) * ctx->blk));
+    MLFF_HIP(ctx, ctx->lr_zpart.alloc(lr_rows_groups(k) * ctx->blk));
   if (ctx->lr_cluster) {
     const size_t ns = (size_t)k * lr_cluster_members(ctx->blk) * 2;
-    MLFF_HIP(ctx, hipMalloc(&ctx->lr_zpart, sizeof(double) * ctx->lr_q * ctx->blk));
-    MLFF_HIP(ctx, hipMalloc(&ctx->lr_slots, sizeof(unsigned long long) * ns));
+    MLFF_HIP(ctx, ctx->lr_zpart.alloc(ctx->lr_q * ctx->blk));
+    MLFF_HIP(ctx, ctx->lr_slots.alloc((int64_t)ns));
     MLFF_HIP(ctx, hipMemsetAsync(ctx->lr_slots, 0, sizeof(unsigned long long) * ns, ctx->stream));
-    MLFF_HIP(ctx, hipMalloc(&ctx->lr_fault, sizeof(int)));
+    MLFF_HIP(ctx, ctx->lr_fault.alloc(1));
     MLFF_HIP(ctx, hipMemsetAsync(ctx->lr_fault, 0, sizeof(int), ctx->stream));
     ctx->lr_epoch = 0;
   }
@@ -765,7 +743,7 @@ int resolve_storage(mlff_ctx *ctx) {
     if (fails > 0.0 && rc == MLFF_OK) symmetric = false;
   }
   if (rc != MLFF_OK || !symmetric) {
-    sym_free(ctx->sym);
+    ctx->sym = SymPack{};
     (void)hipGetLastError();
     ctx->use_sym = false;
     if (explicit_sym) {
@@ -1143,29 +1121,24 @@ int mlff_comm_selftest(int device, int64_t count, double *max_err_out) {
   // releases the buffers, the communicator, the stream and the context
   struct Owned {
     mlff_ctx *ctx = new mlff_ctx();
-    double *a = nullptr, *b = nullptr;
-    ~Owned() {
-      dev_free(a);
-      dev_free(b);
-      mlff_ctx_destroy(ctx);
-    }
+    ~Owned() { mlff_ctx_destroy(ctx); }
   } own;
+  DevBuf<double> a, b;  // declared after the context: released before it
   mlff_ctx *ctx = own.ctx;
   ctx->device = device;
   ctx->rank = 0;
   ctx->world = 1;
-  double *&a = own.a, *&b = own.b;
-  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess)
+  if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream.h, hipStreamNonBlocking) != hipSuccess)
     return set_error(nullptr, MLFF_ERR_HIP, "stream create failed");
   ncclUniqueId id;
   ncclResult_t e = ncclGetUniqueId(&id);
-  if (e == ncclSuccess) e = ncclCommInitRank(&ctx->comm, 1, id, 0);
+  if (e == ncclSuccess) e = ncclCommInitRank(&ctx->comm.h, 1, id, 0);
   if (e != ncclSuccess) {
-    ctx->comm = nullptr;
+    ctx->comm.h = nullptr;
     return set_error(nullptr, MLFF_ERR_COMM, std::string("ncclCommInitRank: ") + ncclGetErrorString(e));
   }
   const size_t n = (size_t)count;
-  if (hipMalloc(&a, sizeof(double) * n) != hipSuccess || hipMalloc(&b, sizeof(double) * n) != hipSuccess)
+  if (a.alloc(count) != hipSuccess || b.alloc(count) != hipSuccess)
     return set_error(nullptr, MLFF_ERR_NOMEM, "device allocation failed");
   std::vector<double> h(n);
   double worst = 0.0;
@@ -1253,7 +1226,7 @@ int mlff_ctx_create(int device, int rank, int world, const unsigned char *comm_i
     return rc;
   };
   if (hipSetDevice(device) != hipSuccess) return fail(set_error(nullptr, MLFF_ERR_HIP, "hipSetDevice failed"));
-  if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess)
+  if (hipStreamCreateWithFlags(&ctx->stream.h, hipStreamNonBlocking) != hipSuccess)
     return fail(set_error(nullptr, MLFF_ERR_HIP, "hipStreamCreate failed"));
   if (world > 1 && std::memcmp(comm_id, "SOLO:", 5) == 0) {
     ctx->solo = true;
@@ -1264,32 +1237,27 @@ int mlff_ctx_create(int device, int rank, int world, const unsigned char *comm_i
   } else if (world > 1) {
     ncclUniqueId id;
     std::memcpy(&id, comm_id, 128);
-    const ncclResult_t e = ncclCommInitRank(&ctx->comm, world, id, rank);
+    const ncclResult_t e = ncclCommInitRank(&ctx->comm.h, world, id, rank);
     if (e != ncclSuccess) {
-      ctx->comm = nullptr;
+      ctx->comm.h = nullptr;
       return fail(set_error(nullptr, MLFF_ERR_COMM, std::string("ncclCommInitRank: ") + ncclGetErrorString(e)));
     }
   }
-  double **vecs[] = {&ctx->x, &ctx->r, &ctx->z, &ctx->q, &ctx->b};
-  for (double **v : vecs) {
-    if (hipMalloc(v, sizeof(double) * ctx->blk) != hipSuccess) return fail(set_error(nullptr, MLFF_ERR_NOMEM, "alloc"));
-    hipMemset(*v, 0, sizeof(double) * ctx->blk);
+  for (DevBuf<double> *v : {&ctx->x, &ctx->r, &ctx->z, &ctx->q, &ctx->b}) {
+    if (v->alloc(ctx->blk) != hipSuccess) return fail(set_error(nullptr, MLFF_ERR_NOMEM, "alloc"));
+    hipMemset(v->get(), 0, sizeof(double) * ctx->blk);
   }
   // full-length operands are padded to whole tiles (entries >= ld stay zero)
   const int64_t ldp = round_up(ctx->ld, kSymTile);
-  if (hipMalloc(&ctx->p_full, sizeof(double) * ldp) != hipSuccess ||
-      hipMalloc(&ctx->xg, sizeof(double) * ldp) != hipSuccess ||
-      hipMalloc(&ctx->part, sizeof(double) * 4 * kMaxPart) != hipSuccess ||
-      hipMalloc(&ctx->st, sizeof(DevState)) != hipSuccess ||
-      hipHostMalloc(&ctx->h_st, sizeof(DevState)) != hipSuccess ||
-      hipMalloc(&ctx->dwork, sizeof(double) * ctx->blk) != hipSuccess ||
-      hipMalloc(&ctx->pivflag, sizeof(int) * ctx->blk) != hipSuccess ||
-      hipMalloc(&ctx->perm, sizeof(int64_t) * n_global) != hipSuccess)
+  if (ctx->p_full.alloc(ldp) != hipSuccess || ctx->xg.alloc(ldp) != hipSuccess ||
+      ctx->part.alloc(4 * kMaxPart) != hipSuccess || ctx->st.alloc(1) != hipSuccess ||
+      ctx->h_st.alloc(1) != hipSuccess || ctx->dwork.alloc(ctx->blk) != hipSuccess ||
+      ctx->pivflag.alloc(ctx->blk) != hipSuccess || ctx->perm.alloc(n_global) != hipSuccess)
     return fail(set_error(nullptr, MLFF_ERR_NOMEM, "device allocation failed"));
   {
     // the gather buffer: z | rho partials per rank (one rank: the fused tile iteration's operand)
     ctx->gstride = ctx->blk + kVecGrid;
-    if (hipMalloc(&ctx->gb, sizeof(double) * world * ctx->gstride) != hipSuccess)
+    if (ctx->gb.alloc(world * ctx->gstride) != hipSuccess)
       return fail(set_error(nullptr, MLFF_ERR_NOMEM, "device allocation failed"));
     hipMemset(ctx->gb, 0, sizeof(double) * world * ctx->gstride);
   }
@@ -1297,7 +1265,7 @@ int mlff_ctx_create(int device, int rank, int world, const unsigned char *comm_i
   hipMemset(ctx->xg, 0, sizeof(double) * ldp);
   hipMemset(ctx->part, 0, sizeof(double) * 4 * kMaxPart);
   hipMemset(ctx->st, 0, sizeof(DevState));
-  std::memset(ctx->h_st, 0, sizeof(DevState));
+  std::memset(ctx->h_st.get(), 0, sizeof(DevState));
   if (hipDeviceSynchronize() != hipSuccess) return fail(set_error(nullptr, MLFF_ERR_HIP, "init sync failed"));
   *ctx_out = ctx;
   return MLFF_OK;
@@ -1309,22 +1277,7 @@ int mlff_ctx_destroy(mlff_ctx *ctx) {
   if (ctx == nullptr) return MLFF_OK;
   hipSetDevice(ctx->device);
   if (ctx->stream) hipStreamSynchronize(ctx->stream);
-  for (void *p : {(void *)ctx->K, (void *)ctx->x, (void *)ctx->r, (void *)ctx->z, (void *)ctx->q,
-                  (void *)ctx->b, (void *)ctx->p_full, (void *)ctx->xg, (void *)ctx->part,
-                  (void *)ctx->st, (void *)ctx->trace, (void *)ctx->T, (void *)ctx->tpart_base,
-                  (void *)ctx->perm, (void *)ctx->dwork, (void *)ctx->pivflag, (void *)ctx->prow, (void *)ctx->zpart, (void *)ctx->lr_zpart, (void *)ctx->lr_slots, (void *)ctx->lr_fault, (void *)ctx->gb})
-    dev_free(p);
-  for (const auto &c : ctx->scratch_chunks) dev_free(c.p);
-  ctx->scratch_chunks.clear();
-  sym_free(ctx->sym);
-  mf_free(ctx->mf);
-  pred_free(ctx->pred);
-  rbf_free(ctx);
-  if (ctx->h_st) hipHostFree(ctx->h_st);
-  for (hipEvent_t e : ctx->timing.ev) hipEventDestroy(e);
-  if (ctx->comm) ncclCommDestroy(ctx->comm);
-  ctx->local.reset();
-  if (ctx->stream) hipStreamDestroy(ctx->stream);
+  // the members release themselves in the order mlff_ctx declares (common.h)
   delete ctx;
   return MLFF_OK;
   MLFF_API_END(ctx)
@@ -1338,7 +1291,7 @@ int mlff_comm_abort(mlff_ctx *ctx) {
   if (ctx->comm != nullptr) {
     (void)hipSetDevice(ctx->device);
     ncclCommAbort(ctx->comm);
-    ctx->comm = nullptr;
+    ctx->comm.h = nullptr;
   }
   return MLFF_OK;
   MLFF_API_END(ctx)
@@ -1396,7 +1349,7 @@ int mlff_set_matrix_host(mlff_ctx *ctx, const double *K_local, int64_t ld_host) 
   ctx->has_matrix = true;
   ctx->K_symmetric = false;
   ctx->sym.ready = false;
-  mf_free(ctx->mf);
+  ctx->mf = MfData();
   rbf_free(ctx);
   return MLFF_OK;
   MLFF_API_END(ctx)
@@ -1446,15 +1399,12 @@ int mlff_gen_rbf(mlff_ctx *ctx, const double *X, int d, double length_scale, dou
   // diagonal and (for the DENSE storage only) the rows are evaluated from them on device
   std::vector<double> Xs((size_t)ctx->N * d);
   for (size_t i = 0; i < Xs.size(); ++i) Xs[i] = X[i] / length_scale;
-  sym_free(ctx->sym);
-  mf_free(ctx->mf);
+  ctx->sym = SymPack{};
+  ctx->mf = MfData();
   rbf_free(ctx);
-  if (ctx->K != nullptr) {  // a dense matrix set earlier is not this kernel
-    (void)hipFree(ctx->K);
-    ctx->K = nullptr;
-  }
+  ctx->K.reset();  // a dense matrix set earlier is not this kernel
   ctx->has_matrix = false;
-  MLFF_HIP(ctx, hipMalloc(&ctx->rbf.Xs, sizeof(double) * Xs.size()));
+  MLFF_HIP(ctx, ctx->rbf.Xs.alloc((int64_t)Xs.size()));
   MLFF_HIP(ctx, hipMemcpy(ctx->rbf.Xs, Xs.data(), sizeof(double) * Xs.size(), hipMemcpyHostToDevice));
   ctx->rbf.d = d;
   ctx->rbf.jitter = jitter;
@@ -1758,7 +1708,7 @@ int mlff_set_storage(mlff_ctx *ctx, int mode) {
     ctx->storage = mode;
     ctx->use_sym = false;
     ctx->use_mf = false;
-    if (mode == MLFF_STORAGE_DENSE || mode == MLFF_STORAGE_MATFREE) sym_free(ctx->sym);
+    if (mode == MLFF_STORAGE_DENSE || mode == MLFF_STORAGE_MATFREE) ctx->sym = SymPack{};
   }
   return MLFF_OK;
   MLFF_API_END(ctx)
@@ -1846,9 +1796,7 @@ int mlff_precon_pivchol(mlff_ctx *ctx, int64_t k, int build_woodbury, int64_t *i
   const auto t0 = std::chrono::steady_clock::now();
   ctx->precon_kind = MLFF_PRECON_NONE;
   MLFF_TRY(alloc_panel(ctx, k));
-  if (ctx->prow) hipFree(ctx->prow);
-  ctx->prow = nullptr;
-  MLFF_HIP(ctx, hipMalloc(&ctx->prow, sizeof(double) * (k + 1)));
+  MLFF_HIP(ctx, ctx->prow.alloc(k + 1));
   MLFF_TRY(pivoted_cholesky(ctx, k, index_columns_out));
   ctx->k = k;  // without Woodbury the panel holds L^T (mlff_precon_get_panel), unused by PCG
   ctx->piv_woodbury_s = 0.0;
@@ -2070,14 +2018,10 @@ int mlff_lev_scores(mlff_ctx *ctx, const int64_t *idx, int64_t k, double lam, do
   if (!(lam > 0.0) || scores_out == nullptr) return set_error(ctx, MLFF_ERR_ARG, "lev_scores: bad args");
   MLFF_TRY(check_idx(ctx, idx, k));
   hipStream_t s = ctx->stream;
-  double *W = nullptr;
-  MLFF_HIP(ctx, hipMalloc(&W, sizeof(double) * round_up(k, 8) * ctx->blk));
+  DevBuf<double> W;  // released on every return
+  MLFF_HIP(ctx, W.alloc(round_up(k, 8) * ctx->blk));
   MLFF_HIP(ctx, hipMemsetAsync(W, 0, sizeof(double) * round_up(k, 8) * ctx->blk, s));
-  int rc = nystrom_panel(ctx, idx, k, 0, lam, W);
-  if (rc != MLFF_OK) {
-    hipFree(W);
-    return rc;
-  }
+  MLFF_TRY(nystrom_panel(ctx, idx, k, 0, lam, W));
   MLFF_HIP(ctx, hipMemsetAsync(ctx->xg, 0, sizeof(double) * ctx->ld, s));
   launch_colsumsq(W, k, ctx->nrows, ctx->blk, ctx->xg + (int64_t)ctx->rank * ctx->blk, s);
   MLFF_TRY(allgather_blocks(ctx, ctx->xg));
@@ -2089,7 +2033,6 @@ int mlff_lev_scores(mlff_ctx *ctx, const int64_t *idx, int64_t k, double lam, do
                                  sizeof(double) * cnt, hipMemcpyDeviceToHost, s));
   }
   MLFF_HIP(ctx, hipStreamSynchronize(s));
-  hipFree(W);
   return MLFF_OK;
   MLFF_API_END(ctx)
 }
@@ -2104,12 +2047,10 @@ int mlff_pcg_start(mlff_ctx *ctx, const double *b_local, const double *x0_local,
   MLFF_TRY(resolve_storage(ctx));
   hipStream_t s = ctx->stream;
   if (ctx->trace_cap < maxiter + 1) {
-    if (ctx->trace) hipFree(ctx->trace);
-    ctx->trace = nullptr;
-    MLFF_HIP(ctx, hipMalloc(&ctx->trace, sizeof(double) * (maxiter + 1)));
+    MLFF_HIP(ctx, ctx->trace.alloc(maxiter + 1));
     ctx->trace_cap = maxiter + 1;
   }
-  for (double *v : {ctx->b, ctx->x, ctx->r, ctx->z, ctx->q})
+  for (double *v : {ctx->b.get(), ctx->x.get(), ctx->r.get(), ctx->z.get(), ctx->q.get()})
     MLFF_HIP(ctx, hipMemsetAsync(v, 0, sizeof(double) * ctx->blk, s));
   MLFF_HIP(ctx, hipMemsetAsync(ctx->p_full, 0, sizeof(double) * ctx->ld, s));
   if (ctx->gb != nullptr)
@@ -2332,6 +2273,14 @@ int mlff_device_memory(mlff_ctx *ctx, int64_t *free_out, int64_t *total_out) {
   if (total_out) *total_out = (int64_t)tot;
   return MLFF_OK;
   MLFF_API_END(ctx)
+}
+
+int mlff_live_bytes(int64_t *bytes_out) {
+  MLFF_API_BEGIN
+  if (bytes_out == nullptr) return set_error(nullptr, MLFF_ERR_ARG, "null pointer");
+  *bytes_out = live_bytes.load();
+  return MLFF_OK;
+  MLFF_API_END(nullptr)
 }
 
 int mlff_timing_reset(mlff_ctx *ctx) {

@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
+#include <atomic>
 #include <cstdint>
 #include <memory>
 #include <string>
@@ -24,6 +25,72 @@ constexpr int kVecGrid = 512;     // workgroups of the grid-stride vector kernel
 constexpr int kSymTile = 512;     // tile edge of the symmetric tiled operator
 
 __host__ __device__ inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
+
+}  // namespace mlff
+
+struct mlff_ctx;
+
+namespace mlff {
+
+int set_error(mlff_ctx *ctx, int code, const std::string &msg);
+
+// Owner of one device allocation (Pinned: of one pinned host allocation); null by default,
+// move-only, freed by its destructor.  It converts to the raw pointer, so launches, copies and
+// pointer arithmetic take it as they take a pointer (.get() where a template deduces from it).
+// Every owning pointer of the library is one of these; views into a buffer and the structs handed
+// to kernels by value hold raw pointers (the deleted copy refuses an owner inside one).
+inline std::atomic<int64_t> live_bytes{0};  // held by all owners of the process (mlff_live_bytes)
+template <typename T, bool Pinned = false>
+class DevBuf {
+ public:
+  DevBuf() = default;
+  DevBuf(const DevBuf &) = delete;
+  DevBuf &operator=(const DevBuf &) = delete;
+  DevBuf(DevBuf &&o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr; }
+  DevBuf &operator=(DevBuf &&o) noexcept {
+    if (this != &o) {
+      reset();
+      p_ = o.p_;
+      bytes_ = o.bytes_;
+      o.p_ = nullptr;
+    }
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  void reset() {
+    if (p_ == nullptr) return;
+    (void)(Pinned ? hipHostFree(p_) : hipFree(p_));
+    live_bytes -= (int64_t)bytes_;
+    p_ = nullptr;
+  }
+  T *get() const { return p_; }
+  operator T *() const { return p_; }
+  T *operator->() const { return p_; }  // ctx->st->status, ctx->h_st->iters
+  // release what is held, then allocate `count` elements (0: one); failure leaves null.  The
+  // first form is for MLFF_HIP (hip_check's code and text), the second reports MLFF_ERR_NOMEM
+  hipError_t alloc(int64_t count) {
+    reset();
+    const size_t bytes = sizeof(T) * (size_t)(count > 0 ? count : 1);
+    void *p = nullptr;
+    const hipError_t e = Pinned ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes);
+    if (e != hipSuccess) return e;
+    p_ = static_cast<T *>(p);
+    bytes_ = bytes;
+    live_bytes += (int64_t)bytes;
+    return hipSuccess;
+  }
+  int alloc(mlff_ctx *ctx, int64_t count, const char *what) {
+    if (alloc(count) == hipSuccess) return MLFF_OK;
+    return set_error(ctx, MLFF_ERR_NOMEM,
+                     std::string(what) + (Pinned ? ": pinned host allocation failed" : ": device allocation failed"));
+  }
+
+ private:
+  T *p_ = nullptr;
+  size_t bytes_ = 0;
+};
+template <typename T>
+using PinBuf = DevBuf<T, true>;
 
 // PCG status values kept on the device (status gating: every kernel of an
 // iteration returns immediately unless status == RUNNING).
@@ -89,26 +156,26 @@ constexpr int kSymCuWords = 4096;
 // Lower-block-triangle tiles of K owned by this rank (kernels_sym.hip).
 struct SymPack {
   bool ready = false;
-  double *tiles = nullptr;   // ntiles x B x B
-  int2 *list = nullptr;      // (I, J) of each stored tile, I >= J
+  DevBuf<double> tiles;      // ntiles x B x B
+  DevBuf<int2> list;         // (I, J) of each stored tile, I >= J
   int64_t ntiles = 0;
   int64_t Np = 0;            // padded global length (multiple of B)
   int64_t nb = 0;            // Np / B
   int64_t tiles_per_rank = 0;
-  double *P = nullptr;       // slot buffer nb x Np
+  DevBuf<double> P;          // slot buffer nb x Np
   // the last (ntiles - nwhole) tiles of `list` run as 2^lsub sub-unit workgroups each;
   // their column partials of sub-units 1.. go to Pq (2^lsub - 1 planes of nb x Np)
   int64_t nwhole = 0;
   int lsub = 2;              // split tiles run as 2^lsub sub-units (row slices) each
   int64_t pq_planes = 0;     // planes allocated in Pq (2^lsub - 1 needed)
-  double *Pq = nullptr;
-  unsigned char *split = nullptr;  // nb x nb: tile (I, J) is split
+  DevBuf<double> Pq;
+  DevBuf<unsigned char> split;     // nb x nb: tile (I, J) is split
   // nb x nb owned slots per row block (sym_own_entry) + nb counts (W > 1)
-  int *own = nullptr;
+  DevBuf<int> own;
   // the same slots as a flat load list per row block (W > 1, k_sym_reduce_wl): entries
   // sym_plist_entry(slot, plane) (plane 0 = P, h >= 1 = Pq plane h - 1; a split slot's planes
   // follow it), pstride entries per row block, then nb counts; pmax = the largest count
-  int *plist = nullptr;
+  DevBuf<int> plist;
   int64_t pstride = 0;
   int pmax = 0;
   bool pq_ordered = false;         // k_sym_reduce_wl's arrival ordered (MLFF_SYM_PQ_ORDERED=1)
@@ -116,11 +183,11 @@ struct SymPack {
   int64_t dyn = 0;                 // > 0: k_symv_dyn with this many workgroups
   int wgs = 0;                     // ... which is this many resident workgroups on every CU
   bool rb4 = false;                // the three-workgroup form (k_symv_dyn<true, 4>, MLFF_SYM_WGS)
-  unsigned long long *ticket = nullptr;  // its work counters (reset by the slot reduction)
+  DevBuf<unsigned long long> ticket;     // its work counters (reset by the slot reduction)
   bool gen = false;                // k_symv_dyn with a generating role (RBF source, sym_build)
   SymGen gsrc;                     // its source and the share of the two roles
-  double *yg = nullptr;      // world > 1: this rank's partial y, rank blocks of ystride
-  double *yr = nullptr;      // world > 1: reduce-scatter result (ystride)
+  DevBuf<double> yg;         // world > 1: this rank's partial y, rank blocks of ystride
+  DevBuf<double> yr;         // world > 1: reduce-scatter result (ystride)
   int64_t ystride = 0;       // blk + tail (p.q shares of every rank)
 };
 
@@ -148,15 +215,15 @@ struct MfData {
   int n = 0, n_perms = 0;
   double sig = 0.0;
   int64_t i0 = 0, ni = 0;            // training points touched by this rank's rows
-  double *Rd = nullptr, *Rdd = nullptr;   // M x D, M x D x 3
-  double *Rt = nullptr, *Zt = nullptr;    // (M n_perms) x D
-  int32_t *Pt = nullptr, *ps = nullptr, *pt = nullptr;
+  DevBuf<double> Rd, Rdd;                 // M x D, M x D x 3
+  DevBuf<double> Rt, Zt;                  // (M n_perms) x D
+  DevBuf<int32_t> Pt, ps, pt;
   bool ident = false;                     // one identity permutation: Rt == Rd, Pt unused
-  double *m5 = nullptr, *w = nullptr;     // ni x (M n_perms), x independent
-  double *c = nullptr, *F = nullptr;      // ni x (M n_perms), ni x D scratch
-  double *part = nullptr;                 // nz x ni x (M n_perms) pair partial sums
-  double *ypart = nullptr;                // J^T partial rows (slices x nrows)
-  double *xc = nullptr;                   // contiguous operand (world > 1)
+  DevBuf<double> m5, w;                   // ni x (M n_perms), x independent
+  DevBuf<double> c, F;                    // ni x (M n_perms), ni x D scratch
+  DevBuf<double> part;                    // nz x ni x (M n_perms) pair partial sums
+  DevBuf<double> ypart;                   // J^T partial rows (slices x nrows)
+  DevBuf<double> xc;                      // contiguous operand (world > 1)
   int nz = 1;                             // descriptor slices of the pair sums
   int64_t dslice = 0;
   std::vector<int32_t> perms, piinv;      // host copies (diagonal blocks)
@@ -164,8 +231,8 @@ struct MfData {
   // (local point, point, permutation), ni x M x n_perms x (6 n + 2), and device atom maps;
   // null when the table would exceed kMfColTableBytes (columns then go through the
   // whole operator)
-  double *uvk = nullptr;
-  int32_t *pi_d = nullptr, *piinv_d = nullptr;
+  DevBuf<double> uvk;
+  DevBuf<int32_t> pi_d, piinv_d;
   // record-factored operator (kernels_mf.hip k_rec_g / k_rec_fin), used when uvk exists:
   // wt = w transposed ((M n_perms) x ni), sv = the per-application pair scalars
   // 5 m (v . x_j) (ni x M n_perms), rpart = J^T G partial rows of every pair block
@@ -175,19 +242,19 @@ struct MfData {
   bool rec_wc16 = true;   // k_rec_g w / x staged as one 16-slot chunk when MP <= 16 (MLFF_REC_WC16)
   int rblk = 0;
   int64_t ldw = 0;
-  double *wt = nullptr, *sv = nullptr, *rpart = nullptr;
+  DevBuf<double> wt, sv, rpart;
   // pair-tile form (kernels_pt.hip k_pt_pair / k_pt_fin; few atoms, D <= 288): in use when
   // ptile is set (the default where it exists; MLFF_MF_FORM=rec|pair|pt overrides); pt_S chunks
   // of the (j, p) range, ptpart = pt_S x ni x (padded D) partial F
   bool ptile = false;
   int pt_S = 1;
-  double *ptpart = nullptr;
+  DevBuf<double> ptpart;
   // energy constraints (use_E_cstr, train.py:212-236; iterative_solver.py:423-440): the
   // operand and result carry M energy entries after the nF = 3 n M force entries (one rank)
   bool E = false;
   int64_t nF = 0;
-  double *kee = nullptr;    // ni x M: sum_p (1 + nrm/sig (1 + nrm/(3 sig))) exp(-nrm/sig)
-  double *eterm = nullptr;  // ni x (M n_perms): a_ijp w_ijp of the last application
+  DevBuf<double> kee;       // ni x M: sum_p (1 + nrm/sig (1 + nrm/(3 sig))) exp(-nrm/sig)
+  DevBuf<double> eterm;     // ni x (M n_perms): a_ijp w_ijp of the last application
 };
 
 // Trained sGDML model held for prediction at new geometries (kernels_predict.hip): the
@@ -203,27 +270,30 @@ struct PredData {
   int G = 1;               // queries per workgroup of the pair stage
   int64_t slab = 0;        // queries per pass (bounds part)
   int64_t PS = 0, ecol = 0;  // row stride of part, column of the energy partial
-  double *Rt = nullptr, *Zt = nullptr;      // MP x D
-  double *Et = nullptr;                     // MP: alphas_E[j] per row (use_E_cstr models), else null
-  double *Rq = nullptr;                    // slab x n x 3 query geometries
-  double *Rdq = nullptr, *Rddq = nullptr;   // slab x D, slab x D x 3
-  double *part = nullptr;                   // S x slab x PS chunk partials
-  double *Fd = nullptr;                     // slab x D
-  double *EF = nullptr;                     // results of a slab: E (slab) then F (slab x 3 n)
-  double *h_in = nullptr, *h_out = nullptr; // pinned staging of Rq and EF: one copy each way
-  // Hessians (kernels_predict_hess.hip): allocated by the first mlff_predict_hessian
-  bool hs_ready = false;
-  int hs_S = 1;                             // chunks of the (j, p) range: fixed by MP
-  int hs_tb = 1;                            // rows per step of the pair stage: fixed by n
-  int hs_stage = 0;                         // > 0: the staged pair stage (k_hs_pair_s) with this many rows
-  bool hs_fd = false;                       // the Hessian's pair stage forms Fd itself (D <= 512)
-  int64_t hs_slab = 0;                      // queries per pass (<= slab)
-  int64_t hs_nblk = 0;                      // 4 x 4 blocks of the lower triangle of H
-  int64_t hs_PS = 0;                        // row of the partials: 16 hs_nblk + 2 (+ D for Fd)
-  double *hs_part = nullptr;                // hs_S x hs_slab x hs_PS chunk partials
-  double *hs_sum = nullptr;                 // hs_slab x hs_PS
-  double *hs_H = nullptr;                   // hs_slab x 3n x 3n
-  double *hs_h_out = nullptr;               // pinned staging of hs_H
+  DevBuf<double> Rt, Zt;                    // MP x D
+  DevBuf<double> Et;                        // MP: alphas_E[j] per row (use_E_cstr models), else null
+  DevBuf<double> Rq;                       // slab x n x 3 query geometries
+  DevBuf<double> Rdq, Rddq;                 // slab x D, slab x D x 3
+  DevBuf<double> part;                      // S x slab x PS chunk partials
+  DevBuf<double> Fd;                        // slab x D
+  DevBuf<double> EF;                        // results of a slab: E (slab) then F (slab x 3 n)
+  PinBuf<double> h_in, h_out;               // pinned staging of Rq and EF: one copy each way
+  // Hessians (kernels_predict_hess.hip): allocated by the first mlff_predict_hessian;
+  // hs = Hess{} releases them
+  struct Hess {
+    bool ready = false;
+    int S = 1;                             // chunks of the (j, p) range: fixed by MP
+    int tb = 1;                            // rows per step of the pair stage: fixed by n
+    int stage = 0;                         // > 0: the staged pair stage (k_hs_pair_s) with this many rows
+    bool fd = false;                       // the Hessian's pair stage forms Fd itself (D <= 512)
+    int64_t slab = 0;                      // queries per pass (<= the prediction's slab)
+    int64_t nblk = 0;                      // 4 x 4 blocks of the lower triangle of H
+    int64_t PS = 0;                        // row of the partials: 16 nblk + 2 (+ D for Fd)
+    DevBuf<double> part;                   // S x slab x PS chunk partials
+    DevBuf<double> sum;                    // slab x PS
+    DevBuf<double> H;                      // slab x 3n x 3n
+    PinBuf<double> h_out;                  // pinned staging of H
+  } hs;
 };
 
 // Synthetic RBF kernel source (tools/utils.py:173-187): the points, scaled by 1 / length
@@ -232,7 +302,7 @@ struct PredData {
 // dense N x N copy exists unless the DENSE storage asks for it (mlff_gen_rbf).
 struct RbfData {
   bool ready = false;
-  double *Xs = nullptr;  // N x d
+  DevBuf<double> Xs;  // N x d
   int d = 0;
   double jitter = 0.0;
 };
@@ -332,6 +402,34 @@ struct Timing {
   int64_t iter_count = 0;
   double comm_ms = 0.0;    // collectives of the sharded iteration (one rank's stream)
   int64_t comm_count = 0;
+  Timing() = default;
+  Timing(const Timing &) = delete;
+  Timing &operator=(const Timing &) = delete;
+  ~Timing() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+};
+
+// The context's stream and RCCL communicator, destroyed with the context (mlff_ctx: last).
+struct StreamHandle {
+  hipStream_t h = nullptr;
+  StreamHandle() = default;
+  StreamHandle(const StreamHandle &) = delete;
+  StreamHandle &operator=(const StreamHandle &) = delete;
+  ~StreamHandle() {
+    if (h != nullptr) (void)hipStreamDestroy(h);
+  }
+  operator hipStream_t() const { return h; }
+};
+struct CommHandle {
+  ncclComm_t h = nullptr;  // nulled by mlff_comm_abort
+  CommHandle() = default;
+  CommHandle(const CommHandle &) = delete;
+  CommHandle &operator=(const CommHandle &) = delete;
+  ~CommHandle() {
+    if (h != nullptr) (void)ncclCommDestroy(h);
+  }
+  operator ncclComm_t() const { return h; }
 };
 
 
@@ -468,6 +566,11 @@ namespace mlff {
 struct LocalGroup;  // in-process transport (api.hip), see comm_allreduce
 }
 
+// The declaration order of the members is the teardown order, reversed: mlff_ctx_destroy sets
+// the device, synchronises the stream and deletes, and C++ destroys the members last to first.
+// So the stream, the local group and the communicator stand first (destroyed last: the
+// communicator, then the group, then the stream), and every buffer and the timing events after
+// them (released before the communicator, in no order that matters among themselves).
 struct mlff_ctx {
   int device = 0, rank = 0, world = 1;
   int64_t N = 0;        // kernel size
@@ -475,13 +578,13 @@ struct mlff_ctx {
   int64_t row0 = 0, nrows = 0;
   int64_t blk = 0;      // padded local length (multiple of 64) = column block per rank
   int64_t ld = 0;       // world * blk: padded global length / K leading dimension
-  hipStream_t stream = nullptr;
-  ncclComm_t comm = nullptr;                   // RCCL (one process per GPU)
-  std::shared_ptr<mlff::LocalGroup> local;     // or: ranks as threads of one process
+  mlff::StreamHandle stream;
+  std::shared_ptr<mlff::LocalGroup> local;     // ranks as threads of one process
+  mlff::CommHandle comm;                       // or: RCCL (one process per GPU)
   bool solo = false;                           // or: one rank alone (profiling, api.hip)
 
   // kernel matrix, blk rows x ld columns (padding rows/cols are zero)
-  double *K = nullptr;
+  mlff::DevBuf<double> K;
   bool has_matrix = false;
   double sigma_K = 1.0, lam = 0.0;
   bool has_operator = false;
@@ -496,14 +599,14 @@ struct mlff_ctx {
   mlff::PredData pred;              // trained model for prediction (optional)
 
   // CG vectors.  local: blk entries; p_full / xg: ld entries (rank blocks)
-  double *x = nullptr, *r = nullptr, *z = nullptr, *q = nullptr, *b = nullptr;
-  double *p_full = nullptr, *xg = nullptr;
-  double *gb = nullptr;    // world > 1: allgather buffer, world blocks of gstride
+  mlff::DevBuf<double> x, r, z, q, b;
+  mlff::DevBuf<double> p_full, xg;
+  mlff::DevBuf<double> gb; // world > 1: allgather buffer, world blocks of gstride
   int64_t gstride = 0;     // blk + kVecGrid (z block + its rho partials)
-  double *part = nullptr;  // partial sums: 3 * kMaxPart + tpart (k * S)
-  mlff::DevState *st = nullptr;
-  mlff::DevState *h_st = nullptr;  // pinned mirror
-  double *trace = nullptr;
+  mlff::DevBuf<double> part;  // partial sums: 3 * kMaxPart + tpart (k * S)
+  mlff::DevBuf<mlff::DevState> st;
+  mlff::PinBuf<mlff::DevState> h_st;  // pinned mirror
+  mlff::DevBuf<double> trace;
   int64_t trace_cap = 0;
   bool pcg_active = false;
   int64_t pcg_done = 0;   // iterations known complete on the host side
@@ -512,11 +615,11 @@ struct mlff_ctx {
   // preconditioner
   int precon_kind = MLFF_PRECON_NONE;
   int64_t k = 0;
-  double *T = nullptr;    // k x blk (row stride blk)
+  mlff::DevBuf<double> T; // k x blk (row stride blk)
   double sigma_p = 1.0;   // z = sigma_p * (r - T^T T r) / lam
   int tsplit = 1;         // column splits of the T GEMV
   int zsplit = 1;         // row splits of the T^T t GEMV
-  double *zpart = nullptr;  // zsplit x blk partials
+  mlff::DevBuf<double> zpart;  // zsplit x blk partials
   bool lr_rows = false;        // one-pass low-rank apply (launch_lr_apply_rows), one rank
   // CG vector updates folded into the matrix-free nanotube iteration; read from
   // MLFF_FUSE_P / MLFF_FUSE_XR (=0: separate launches) when the context is created
@@ -538,24 +641,24 @@ struct mlff_ctx {
   bool exact_sums = false;
   bool lr_cluster = false;     // the same for long rows (launch_lr_apply_cluster)
   int lr_q = 0;                // its clusters
-  double *lr_zpart = nullptr;  // lr_rows_groups(k) (or lr_q) x blk partials
-  unsigned long long *lr_slots = nullptr;  // cluster hand-off granules (k x C x 2)
+  mlff::DevBuf<double> lr_zpart;  // lr_rows_groups(k) (or lr_q) x blk partials
+  mlff::DevBuf<unsigned long long> lr_slots;  // cluster hand-off granules (k x C x 2)
   unsigned lr_epoch = 0;       // per cluster launch, never 0 in a launch
-  int *lr_fault = nullptr;     // ST_FAULT when a cluster hand-off timed out (precon_apply)
+  mlff::DevBuf<int> lr_fault;  // ST_FAULT when a cluster hand-off timed out (precon_apply)
   int lr_fallbacks = 0;        // cluster applies that timed out and fell back to two passes
   double last_lo_eig = 0.0;
   bool cho_flipped = false;  // a cho_factor_stable retried upward after a noisy lo > 0
   bool eig_converged = true;   // last truncated eigensolve met kEigTol (kernels_eig.hip)
   double eig_rel_resid = 0.0;  // its worst Ritz residual / |theta_0|    // lo_eig of the last _cho_factor_stable (cho_factor_stable)
-  double *tpart = nullptr;       // = tpart_base + kVecGrid
-  double *tpart_base = nullptr;
+  double *tpart = nullptr;       // view: tpart_base + kVecGrid
+  mlff::DevBuf<double> tpart_base;
   bool spec_t = false;           // tpart already holds T r of the current r (merged collective)
 
   // pivoted Cholesky scratch
-  int64_t *perm = nullptr;   // global permutation (replicated)
-  double *dwork = nullptr;   // residual diagonal (local)
-  int *pivflag = nullptr;    // local rows already pivoted
-  double *prow = nullptr;    // L[m_pi, :m]
+  mlff::DevBuf<int64_t> perm;  // global permutation (replicated)
+  mlff::DevBuf<double> dwork;  // residual diagonal (local)
+  mlff::DevBuf<int> pivflag;   // local rows already pivoted
+  mlff::DevBuf<double> prow;   // L[m_pi, :m]
   std::vector<double> piv_col_s;  // device seconds per column of the last build
   double piv_woodbury_s = 0.0;    // its Woodbury build (G, chol, T)
 
@@ -565,7 +668,7 @@ struct mlff_ctx {
 
   // device scratch arena (ScratchScope / scratch_get): chunks, current chunk and offset
   struct ScratchChunk {
-    char *p;
+    mlff::DevBuf<char> p;
     size_t size;
   };
   std::vector<ScratchChunk> scratch_chunks;
@@ -624,10 +727,9 @@ int api_exception(mlff_ctx *ctx, int code, const char *what);
   }
 
 // Device scratch of a build function, from the context's arena (mlff_ctx::scratch):
-// a bump allocator over chunks obtained once with hipMalloc and kept until
-// mlff_ctx_destroy.  Every user runs on ctx->stream, so memory handed out again after a
+// a bump allocator over chunks allocated once and kept until mlff_ctx_destroy.  Every user runs on ctx->stream, so memory handed out again after a
 // ScratchScope has closed is only touched by kernels ordered after the previous user's.
-// (No stream-ordered allocator: hipMallocAsync pools outlive the contexts' streams.)
+// (No stream-ordered allocator: its pools outlive the contexts' streams.)
 struct ScratchScope {
   mlff_ctx *ctx;
   size_t chunk, off;
@@ -641,13 +743,6 @@ int scratch_get(mlff_ctx *ctx, size_t bytes, void **out);
 template <typename T>
 int scratch_alloc(mlff_ctx *ctx, T **out, size_t count) {
   return scratch_get(ctx, sizeof(T) * (count > 0 ? count : 1), reinterpret_cast<void **>(out));
-}
-// device memory that outlives the call; failure: *p = nullptr, "<what>: device allocation failed"
-template <typename T>
-int dev_alloc(mlff_ctx *ctx, T **p, int64_t count, const char *what) {
-  if (hipMalloc(p, sizeof(T) * (size_t)(count > 0 ? count : 1)) == hipSuccess) return MLFF_OK;
-  *p = nullptr;
-  return set_error(ctx, MLFF_ERR_NOMEM, std::string(what) + ": device allocation failed");
 }
 
 // ---- collectives (api.hip): RCCL, or the in-process transport ---------------
@@ -847,7 +942,6 @@ void launch_sgdml_columns(const double *Rdd, int64_t M, int n, int64_t D, int64_
 // build the tiles this rank owns from the dense rows; check_symmetry compares
 // every tile with its mirror (one rank only)
 int sym_build(mlff_ctx *ctx, bool check_symmetry, bool *symmetric_out);
-void sym_free(SymPack &sp);
 // The search-direction update of the sharded iteration (k_update_p_gathered: p = z + beta p,
 // z and every rank's rho partials in the gather buffer gb) folded into the tile mat-vec: the
 // tile workgroups form the operand entries they read, the slot reduction writes p (gb null:
@@ -936,7 +1030,6 @@ double mf_bytes(const mlff_ctx *ctx);
 // modelled seconds of one application of the matrix-free operator in its form on this rank,
 // from the rates measured on MI355X: the storage choice of MLFF_STORAGE_AUTO
 double mf_seconds(const mlff_ctx *ctx);
-void mf_free(MfData &mf);
 int desc_perm_tables(mlff_ctx *ctx, const int32_t *perms, int n, int n_perms,
                      std::vector<int32_t> &Pt, std::vector<int32_t> &piinv);
 
@@ -952,7 +1045,6 @@ int pred_set_energy_coefficients(mlff_ctx *ctx, const double *alphas_E);
 int pred_run(mlff_ctx *ctx, const double *R, int64_t Q, double *E_out, double *F_out);
 bool pred_tile_supported(int64_t D);
 void pred_work(const PredData &pd, double *flops_per_query, double *bytes_per_query);
-void pred_free(PredData &pd);
 // upload nq <= pred.slab host geometries and run the descriptor stage and, with_fd, the pair and
 // chunk-sum stages: pred.Rq, Rdq, Rddq (and Fd) of those queries are then on the device (in
 // stream order)
@@ -963,7 +1055,6 @@ int pred_fd_slab(mlff_ctx *ctx, const double *R, int64_t nq, bool with_fd);
 // (MLFF_PRED_HESS_SLAB is read there)
 int pred_hess_run(mlff_ctx *ctx, const double *R, int64_t Q, double *H_out);
 void pred_hess_work(const PredData &pd, double *flops_per_query, double *bytes_per_query);
-void pred_hess_free(PredData &pd);
 
 // ---- operator access for the builds (api.hip) --------------------------------
 // require the operator and resolve its storage (builds the tiles if they are to be used)

@@ -653,23 +653,17 @@ constexpr auto k_desc = k_desc_t<false>;
 
 int sgdml_descriptors(const double *R, int64_t M, int n, double *R_desc, double *R_d_desc) {
   const int64_t D = (int64_t)n * (n - 1) / 2;
-  double *dR = nullptr, *dRd = nullptr, *dRdd = nullptr;
-  const int rc = [&]() -> int {
-    if (hipMalloc(&dR, sizeof(double) * M * n * 3) != hipSuccess ||
-        hipMalloc(&dRd, sizeof(double) * M * D) != hipSuccess ||
-        hipMalloc(&dRdd, sizeof(double) * M * D * 3) != hipSuccess)
-      return MLFF_ERR_NOMEM;
-    if (hipMemcpy(dR, R, sizeof(double) * M * n * 3, hipMemcpyHostToDevice) != hipSuccess) return MLFF_ERR_HIP;
-    const unsigned gx = (unsigned)std::min<int64_t>((D + 255) / 256, 64);
-    hipLaunchKernelGGL(k_desc, dim3(gx, (unsigned)M), dim3(256), 0, 0, dR, n, dRd, dRdd);
-    if (hipGetLastError() != hipSuccess ||
-        hipMemcpy(R_desc, dRd, sizeof(double) * M * D, hipMemcpyDeviceToHost) != hipSuccess ||
-        hipMemcpy(R_d_desc, dRdd, sizeof(double) * M * D * 3, hipMemcpyDeviceToHost) != hipSuccess)
-      return MLFF_ERR_HIP;
-    return MLFF_OK;
-  }();
-  for (double *p : {dR, dRd, dRdd}) (void)hipFree(p);  // the one exit (a null pointer is a no-op)
-  return rc;
+  DevBuf<double> dR, dRd, dRdd;
+  if (dR.alloc(M * n * 3) != hipSuccess || dRd.alloc(M * D) != hipSuccess || dRdd.alloc(M * D * 3) != hipSuccess)
+    return MLFF_ERR_NOMEM;
+  if (hipMemcpy(dR, R, sizeof(double) * M * n * 3, hipMemcpyHostToDevice) != hipSuccess) return MLFF_ERR_HIP;
+  const unsigned gx = (unsigned)std::min<int64_t>((D + 255) / 256, 64);
+  hipLaunchKernelGGL(k_desc, dim3(gx, (unsigned)M), dim3(256), 0, 0, dR, n, dRd, dRdd);
+  if (hipGetLastError() != hipSuccess ||
+      hipMemcpy(R_desc, dRd, sizeof(double) * M * D, hipMemcpyDeviceToHost) != hipSuccess ||
+      hipMemcpy(R_d_desc, dRdd, sizeof(double) * M * D * 3, hipMemcpyDeviceToHost) != hipSuccess)
+    return MLFF_ERR_HIP;
+  return MLFF_OK;
 }
 
 }  // namespace mlff

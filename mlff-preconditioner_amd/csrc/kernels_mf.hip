@@ -1090,7 +1090,7 @@ __global__ void k_rec_wt(const double *__restrict__ uvk, int64_t ni, int64_t MP,
 int mf_setup(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc, int64_t M, int n_atoms,
              const int32_t *perms, int n_perms, double sig) {
   MfData &mf = ctx->mf;
-  mf_free(mf);
+  mf = MfData();
   const int n = n_atoms;
   const int64_t D = (int64_t)n * (n - 1) / 2, n3 = 3 * (int64_t)n;
   if (n < 2 || M < 1 || n_perms < 1) return set_error(ctx, MLFF_ERR_ARG, "sgdml operator: bad sizes");
@@ -1122,19 +1122,19 @@ int mf_setup(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc, int64_
   const int64_t MP = M * n_perms;
   const int64_t nic = std::max<int64_t>(mf.ni, 1);
   hipStream_t s = ctx->stream;
-  MLFF_HIP(ctx, hipMalloc(&mf.Rd, sizeof(double) * M * D));
-  MLFF_HIP(ctx, hipMalloc(&mf.Rdd, sizeof(double) * M * D * 3));
-  MLFF_HIP(ctx, hipMalloc(&mf.Rt, sizeof(double) * MP * D));
-  MLFF_HIP(ctx, hipMalloc(&mf.Zt, sizeof(double) * MP * D));
-  MLFF_HIP(ctx, hipMalloc(&mf.Pt, sizeof(int32_t) * n_perms * D));
-  MLFF_HIP(ctx, hipMalloc(&mf.ps, sizeof(int32_t) * D));
-  MLFF_HIP(ctx, hipMalloc(&mf.pt, sizeof(int32_t) * D));
-  MLFF_HIP(ctx, hipMalloc(&mf.m5, sizeof(double) * nic * MP));
-  MLFF_HIP(ctx, hipMalloc(&mf.w, sizeof(double) * nic * MP));
-  MLFF_HIP(ctx, hipMalloc(&mf.c, sizeof(double) * nic * MP));
-  MLFF_HIP(ctx, hipMalloc(&mf.F, sizeof(double) * nic * D));
-  if (ctx->world > 1) MLFF_HIP(ctx, hipMalloc(&mf.xc, sizeof(double) * ctx->N));
-  MLFF_HIP(ctx, hipMalloc(&mf.ypart, sizeof(double) * kJSMax * std::max<int64_t>(ctx->nrows, 1)));
+  MLFF_HIP(ctx, mf.Rd.alloc(M * D));
+  MLFF_HIP(ctx, mf.Rdd.alloc(M * D * 3));
+  MLFF_HIP(ctx, mf.Rt.alloc(MP * D));
+  MLFF_HIP(ctx, mf.Zt.alloc(MP * D));
+  MLFF_HIP(ctx, mf.Pt.alloc(n_perms * D));
+  MLFF_HIP(ctx, mf.ps.alloc(D));
+  MLFF_HIP(ctx, mf.pt.alloc(D));
+  MLFF_HIP(ctx, mf.m5.alloc(nic * MP));
+  MLFF_HIP(ctx, mf.w.alloc(nic * MP));
+  MLFF_HIP(ctx, mf.c.alloc(nic * MP));
+  MLFF_HIP(ctx, mf.F.alloc(nic * D));
+  if (ctx->world > 1) MLFF_HIP(ctx, mf.xc.alloc(ctx->N));
+  MLFF_HIP(ctx, mf.ypart.alloc(kJSMax * std::max<int64_t>(ctx->nrows, 1)));
   MLFF_HIP(ctx, hipMemcpyAsync(mf.Rd, R_desc, sizeof(double) * M * D, hipMemcpyHostToDevice, s));
   MLFF_HIP(ctx, hipMemcpyAsync(mf.Rdd, R_d_desc, sizeof(double) * M * D * 3, hipMemcpyHostToDevice, s));
   MLFF_HIP(ctx, hipMemcpyAsync(mf.Pt, Pt.data(), sizeof(int32_t) * n_perms * D, hipMemcpyHostToDevice, s));
@@ -1156,7 +1156,7 @@ int mf_setup(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc, int64_
   mf.dslice = round_up((D + nz - 1) / nz, kDC);
   mf.nz = (int)((D + mf.dslice - 1) / mf.dslice);
   nz = mf.nz;
-  MLFF_HIP(ctx, hipMalloc(&mf.part, sizeof(double) * nz * nic * MP));
+  MLFF_HIP(ctx, mf.part.alloc(nz * nic * MP));
   // operator form: the pair-tile one where it exists (few atoms), else the record-factored one
   // where the records fit, else the pair sums; MLFF_MF_FORM=pt|rec|pair asks for one (A/B, tests).
   // Decided from the sizes every rank shares (not the local point count), so that the ranks of
@@ -1168,20 +1168,20 @@ int mf_setup(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc, int64_
     mf.ptile = true;
     if (mf.ni > 0) {
       mf.pt_S = pt_chunks(D, mf.ni, MP);
-      MLFF_HIP(ctx, hipMalloc(&mf.ptpart, sizeof(double) * mf.pt_S * mf.ni * pt_padded_d(D)));
+      MLFF_HIP(ctx, mf.ptpart.alloc(mf.pt_S * mf.ni * pt_padded_d(D)));
     }
   }
   // single-column path: the (r = i, s = j) pair records of the local points (3.5 MB for
   // the nanotube, M = 14; ni M n_perms (6 n + 2) doubles in general)
   const double col_bytes = 8.0 * (double)mf.ni * (double)MP * (double)(6 * n + 2);
   if (E) {  // energy tables; columns go through the whole operator (K_op e_g)
-    MLFF_HIP(ctx, hipMalloc(&mf.kee, sizeof(double) * nic * M));
-    MLFF_HIP(ctx, hipMalloc(&mf.eterm, sizeof(double) * nic * MP));
+    MLFF_HIP(ctx, mf.kee.alloc(nic * M));
+    MLFF_HIP(ctx, mf.eterm.alloc(nic * MP));
     launch_sgdml_kee(mf.Rd, M, D, mf.i0, mf.ni, mf.Pt, n_perms, sig, mf.kee, s);
   } else if (mf.ni > 0 && col_bytes <= col_table_cap()) {
-    MLFF_HIP(ctx, hipMalloc(&mf.uvk, (size_t)col_bytes));
-    MLFF_HIP(ctx, hipMalloc(&mf.pi_d, sizeof(int32_t) * n_perms * n));
-    MLFF_HIP(ctx, hipMalloc(&mf.piinv_d, sizeof(int32_t) * n_perms * n));
+    MLFF_HIP(ctx, mf.uvk.alloc(mf.ni * MP * (6 * (int64_t)n + 2)));
+    MLFF_HIP(ctx, mf.pi_d.alloc((int64_t)n_perms * n));
+    MLFF_HIP(ctx, mf.piinv_d.alloc((int64_t)n_perms * n));
     MLFF_HIP(ctx, hipMemcpyAsync(mf.pi_d, perms, sizeof(int32_t) * n_perms * n, hipMemcpyHostToDevice, s));
     MLFF_HIP(ctx, hipMemcpyAsync(mf.piinv_d, piinv.data(), sizeof(int32_t) * n_perms * n,
                                  hipMemcpyHostToDevice, s));
@@ -1194,10 +1194,10 @@ int mf_setup(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc, int64_
       mf.rblk = (n + kRB - 1) / kRB;
       mf.ldw = round_up(mf.ni, kRG);
       const int64_t wrows = round_up(MP, kRJ);
-      MLFF_HIP(ctx, hipMalloc(&mf.wt, sizeof(double) * wrows * mf.ldw));
+      MLFF_HIP(ctx, mf.wt.alloc(wrows * mf.ldw));
       MLFF_HIP(ctx, hipMemsetAsync(mf.wt, 0, sizeof(double) * wrows * mf.ldw, s));
-      MLFF_HIP(ctx, hipMalloc(&mf.sv, sizeof(double) * MP * mf.ni));
-      MLFF_HIP(ctx, hipMalloc(&mf.rpart, sizeof(double) * mf.rblk * mf.ni * n3));
+      MLFF_HIP(ctx, mf.sv.alloc(MP * mf.ni));
+      MLFF_HIP(ctx, mf.rpart.alloc(mf.rblk * mf.ni * n3));
       hipLaunchKernelGGL(k_rec_wt, dim3((unsigned)((mf.ni * MP + 255) / 256)), dim3(256), 0, s,
                          mf.uvk, mf.ni, MP, n, mf.ldw, mf.wt);
       mf.rec = true;
@@ -1398,8 +1398,8 @@ int mf_energies(mlff_ctx *ctx, const double *alphas, double *E_pairs_host) {
   if (mf.E) return set_error(ctx, MLFF_ERR_STATE, "sgdml_energies: not with use_E_cstr");
   hipStream_t s = ctx->stream;
   const int64_t MP = mf.M * mf.n_perms;
-  double *da = nullptr;
-  MLFF_HIP(ctx, hipMalloc(&da, sizeof(double) * ctx->N));
+  DevBuf<double> da;  // released on every return, after the synchronisation on the way out
+  MLFF_HIP(ctx, da.alloc(ctx->N));
   MLFF_HIP(ctx, hipMemcpyAsync(da, alphas, sizeof(double) * ctx->N, hipMemcpyHostToDevice, s));
   const unsigned gx = (unsigned)std::min<int64_t>((mf.D + 255) / 256, 1024);
   hipLaunchKernelGGL(k_mf_z<false>, dim3(gx, (unsigned)MP), dim3(256), 0, s, mf.Rdd, mf.Pt, mf.ps, mf.pt,
@@ -1417,7 +1417,6 @@ int mf_energies(mlff_ctx *ctx, const double *alphas, double *E_pairs_host) {
   }
   MLFF_HIP(ctx, hipGetLastError());
   MLFF_HIP(ctx, hipStreamSynchronize(s));
-  hipFree(da);
   return MLFF_OK;
 }
 
@@ -1500,17 +1499,6 @@ double mf_bytes(const mlff_ctx *ctx) {
   const double chunks = (double)((mf.ni + kIC - 1) / kIC);
   // Zt written once; Rt, Zt read by every point chunk in two kernels; Rd, Rdd, F
   return 8.0 * (MP * D * (1.0 + 4.0 * chunks) + (double)mf.ni * D * 6.0 + 16.0 * ctx->nrows);
-}
-
-void mf_free(MfData &mf) {
-  for (void *p : {(void *)mf.Rd, (void *)mf.Rdd, (void *)mf.Rt, (void *)mf.Zt, (void *)mf.Pt,
-                  (void *)mf.ps, (void *)mf.pt, (void *)mf.m5, (void *)mf.w, (void *)mf.c,
-                  (void *)mf.F, (void *)mf.part, (void *)mf.ypart, (void *)mf.xc,
-                  (void *)mf.uvk, (void *)mf.pi_d, (void *)mf.piinv_d, (void *)mf.kee,
-                  (void *)mf.eterm, (void *)mf.wt, (void *)mf.sv, (void *)mf.rpart,
-                  (void *)mf.ptpart})
-    if (p) (void)hipFree(p);
-  mf = MfData();
 }
 
 }  // namespace mlff

@@ -431,15 +431,6 @@ const PrVariant *pr_variant(int64_t D) {
 
 }  // namespace
 
-void pred_free(PredData &pd) {
-  pred_hess_free(pd);
-  for (double *p : {pd.Rt, pd.Zt, pd.Et, pd.Rq, pd.Rdq, pd.Rddq, pd.part, pd.Fd, pd.EF})
-    if (p != nullptr) (void)hipFree(p);
-  for (double *p : {pd.h_in, pd.h_out})
-    if (p != nullptr) (void)hipHostFree(p);
-  pd = PredData{};
-}
-
 bool pred_tile_supported(int64_t D) { return pr_variant(D) != nullptr; }
 
 int pred_set_model(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc_alpha, int64_t M,
@@ -474,8 +465,8 @@ int pred_set_model(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc_a
     }
   hipStream_t s = ctx->stream;
   MLFF_HIP(ctx, hipStreamSynchronize(s));
-  pred_free(ctx->pred);
   PredData &pd = ctx->pred;
+  pd = PredData{};
   pd.M = M;
   pd.D = D;
   pd.MP = MP;
@@ -511,18 +502,17 @@ int pred_set_model(mlff_ctx *ctx, const double *R_desc, const double *R_d_desc_a
   }
   pd.slab = slab;
   auto fail = [&](int rc) {
-    pred_free(ctx->pred);
+    pd = PredData{};
     return rc;
   };
-  const std::pair<double **, int64_t> bufs[] = {
+  const std::pair<DevBuf<double> *, int64_t> bufs[] = {
       {&pd.Rt, MP * D},         {&pd.Zt, MP * D},           {&pd.Rq, slab * 3 * n},
       {&pd.Rdq, slab * D},      {&pd.Rddq, slab * D * 3},   {&pd.part, (int64_t)pd.S * slab * pd.PS},
       {&pd.Fd, slab * D},       {&pd.EF, slab * (3 * n + 1)}};
   for (const auto &b : bufs)
-    if (const int rc = dev_alloc(ctx, b.first, b.second, "predict")) return fail(rc);
-  if (hipHostMalloc(&pd.h_in, sizeof(double) * slab * 3 * n) != hipSuccess ||
-      hipHostMalloc(&pd.h_out, sizeof(double) * slab * (3 * n + 1)) != hipSuccess)
-    return fail(set_error(ctx, MLFF_ERR_NOMEM, "predict: pinned host allocation failed"));
+    if (const int rc = b.first->alloc(ctx, b.second, "predict")) return fail(rc);
+  if (const int rc = pd.h_in.alloc(ctx, slab * 3 * n, "predict")) return fail(rc);
+  if (const int rc = pd.h_out.alloc(ctx, slab * (3 * n + 1), "predict")) return fail(rc);
   if (hipMemcpy(pd.Rt, hR.data(), sizeof(double) * MP * D, hipMemcpyHostToDevice) != hipSuccess ||
       hipMemcpy(pd.Zt, hZ.data(), sizeof(double) * MP * D, hipMemcpyHostToDevice) != hipSuccess)
     return fail(set_error(ctx, MLFF_ERR_HIP, "predict: model upload failed"));
@@ -534,18 +524,16 @@ int pred_set_energy_coefficients(mlff_ctx *ctx, const double *alphas_E) {
   PredData &pd = ctx->pred;
   MLFF_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (alphas_E == nullptr) {
-    if (pd.Et != nullptr) (void)hipFree(pd.Et);
-    pd.Et = nullptr;
+    pd.Et.reset();
     return MLFF_OK;
   }
   // alphas_E_lin (predict.py:364-368): alphas_E[j] for every permuted copy jp = j n_perms + p
   std::vector<double> hE((size_t)pd.MP);
   for (int64_t j = 0; j < pd.M; ++j)
     for (int p = 0; p < pd.n_perms; ++p) hE[(size_t)(j * pd.n_perms + p)] = alphas_E[j];
-  if (pd.Et == nullptr) MLFF_TRY(dev_alloc(ctx, &pd.Et, pd.MP, "predict"));
+  if (pd.Et == nullptr) MLFF_TRY(pd.Et.alloc(ctx, pd.MP, "predict"));
   if (hipMemcpy(pd.Et, hE.data(), sizeof(double) * pd.MP, hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(pd.Et);
-    pd.Et = nullptr;
+    pd.Et.reset();
     return set_error(ctx, MLFF_ERR_HIP, "predict: upload of the energy coefficients failed");
   }
   return MLFF_OK;

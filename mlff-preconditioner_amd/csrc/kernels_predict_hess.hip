@@ -508,36 +508,32 @@ int hs_n3p(int n) { return (int)round_up(3 * (int64_t)n, 4); }
 // the slab buffers, on the first call after a model is set
 int hs_prepare(mlff_ctx *ctx) {
   PredData &pd = ctx->pred;
-  if (pd.hs_ready) return MLFF_OK;
+  if (pd.hs.ready) return MLFF_OK;
   const int N3P = hs_n3p(pd.n);
   if (N3P > kHsMaxN3P) return set_error(ctx, MLFF_ERR_ARG, "predict hessian: more than 682 atoms");
   const int64_t N3 = 3 * (int64_t)pd.n, NB = N3P / 4;
-  pd.hs_nblk = NB * (NB + 1) / 2;
-  pd.hs_stage = hs_staged_tb(pd.n, pd.D);
-  pd.hs_tb = pd.hs_stage > 0 ? pd.hs_stage : 3 * kHsTB * N3P * 8 <= 48 * 1024 ? kHsTB : 1;
-  pd.hs_S = (int)std::max<int64_t>(1, std::min<int64_t>(kHsMaxChunks, pd.MP / kHsChunkRows));
-  pd.hs_fd = hs_fused(pd.D);
-  pd.hs_PS = 16 * pd.hs_nblk + 2 + (pd.hs_fd ? round_up(pd.D, 2) : 0);
-  const int64_t PS = pd.hs_PS;
+  pd.hs.nblk = NB * (NB + 1) / 2;
+  pd.hs.stage = hs_staged_tb(pd.n, pd.D);
+  pd.hs.tb = pd.hs.stage > 0 ? pd.hs.stage : 3 * kHsTB * N3P * 8 <= 48 * 1024 ? kHsTB : 1;
+  pd.hs.S = (int)std::max<int64_t>(1, std::min<int64_t>(kHsMaxChunks, pd.MP / kHsChunkRows));
+  pd.hs.fd = hs_fused(pd.D);
+  pd.hs.PS = 16 * pd.hs.nblk + 2 + (pd.hs.fd ? round_up(pd.D, 2) : 0);
+  const int64_t PS = pd.hs.PS;
   // queries per pass: the chunk partials within 256 MB, the results within 256 MB, and no more
   // than the prediction's slab (its buffers hold the queries' descriptors and Fd; MLFF_PRED_SLAB
   // thereby bounds this slab too)
-  int64_t slab = ((int64_t)256 << 20) / std::max<int64_t>((int64_t)pd.hs_S * PS * 8, N3 * N3 * 8);
+  int64_t slab = ((int64_t)256 << 20) / std::max<int64_t>((int64_t)pd.hs.S * PS * 8, N3 * N3 * 8);
   slab = std::max<int64_t>(1, std::min<int64_t>(slab, pd.slab));
-  pd.hs_slab = slab;
+  pd.hs.slab = slab;
   int rc;
-  if ((rc = dev_alloc(ctx, &pd.hs_part, (int64_t)pd.hs_S * slab * PS, "predict hessian")) != MLFF_OK ||
-      (rc = dev_alloc(ctx, &pd.hs_sum, slab * PS, "predict hessian")) != MLFF_OK ||
-      (rc = dev_alloc(ctx, &pd.hs_H, slab * N3 * N3, "predict hessian")) != MLFF_OK) {
-    pred_hess_free(pd);
+  if ((rc = pd.hs.part.alloc(ctx, (int64_t)pd.hs.S * slab * PS, "predict hessian")) != MLFF_OK ||
+      (rc = pd.hs.sum.alloc(ctx, slab * PS, "predict hessian")) != MLFF_OK ||
+      (rc = pd.hs.H.alloc(ctx, slab * N3 * N3, "predict hessian")) != MLFF_OK ||
+      (rc = pd.hs.h_out.alloc(ctx, slab * N3 * N3, "predict hessian")) != MLFF_OK) {
+    pd.hs = PredData::Hess{};
     return rc;
   }
-  if (hipHostMalloc(&pd.hs_h_out, sizeof(double) * slab * N3 * N3) != hipSuccess) {
-    pd.hs_h_out = nullptr;
-    pred_hess_free(pd);
-    return set_error(ctx, MLFF_ERR_NOMEM, "predict hessian: pinned host allocation failed");
-  }
-  pd.hs_ready = true;
+  pd.hs.ready = true;
   return MLFF_OK;
 }
 
@@ -554,20 +550,12 @@ HsArgs hs_model_args(const PredData &pd) {
   a.n = pd.n;
   a.N3 = 3 * pd.n;
   a.N3P = hs_n3p(pd.n);
-  a.nblk = (int)pd.hs_nblk;
+  a.nblk = (int)pd.hs.nblk;
   a.mc = matern_consts(pd.sig);
   return a;
 }
 
 }  // namespace
-
-void pred_hess_free(PredData &pd) {
-  for (double *p : {pd.hs_part, pd.hs_sum, pd.hs_H})
-    if (p != nullptr) (void)hipFree(p);
-  if (pd.hs_h_out != nullptr) (void)hipHostFree(pd.hs_h_out);
-  pd.hs_part = pd.hs_sum = pd.hs_H = pd.hs_h_out = nullptr;
-  pd.hs_ready = false;
-}
 
 int pred_hess_run(mlff_ctx *ctx, const double *R, int64_t Q, double *H_out) {
   MLFF_TRY(hs_prepare(ctx));
@@ -577,46 +565,46 @@ int pred_hess_run(mlff_ctx *ctx, const double *R, int64_t Q, double *H_out) {
   HsArgs a = hs_model_args(pd);
   a.Rdq = pd.Rdq;
   a.Rddq = pd.Rddq;
-  a.S = pd.hs_S;
-  a.part = pd.hs_part;
-  a.PS = pd.hs_PS;
+  a.S = pd.hs.S;
+  a.part = pd.hs.part;
+  a.PS = pd.hs.PS;
   const bool ecstr = pd.Et != nullptr;
-  const int TB = pd.hs_tb;
+  const int TB = pd.hs.tb;
   // one row per step means 3n > 256, far past the fused form's D
-  const HsFn fn = pd.hs_stage == 32 ? (ecstr ? k_hs_pair_s<32, true> : k_hs_pair_s<32, false>)
-                  : pd.hs_stage == 16 ? (ecstr ? k_hs_pair_s<16, true> : k_hs_pair_s<16, false>)
-                  : pd.hs_stage == 8 ? (ecstr ? k_hs_pair_s<8, true> : k_hs_pair_s<8, false>)
-                  : TB == kHsTB ? (pd.hs_fd ? (ecstr ? k_hs_pair<kHsTB, true, true> : k_hs_pair<kHsTB, false, true>)
+  const HsFn fn = pd.hs.stage == 32 ? (ecstr ? k_hs_pair_s<32, true> : k_hs_pair_s<32, false>)
+                  : pd.hs.stage == 16 ? (ecstr ? k_hs_pair_s<16, true> : k_hs_pair_s<16, false>)
+                  : pd.hs.stage == 8 ? (ecstr ? k_hs_pair_s<8, true> : k_hs_pair_s<8, false>)
+                  : TB == kHsTB ? (pd.hs.fd ? (ecstr ? k_hs_pair<kHsTB, true, true> : k_hs_pair<kHsTB, false, true>)
                                           : (ecstr ? k_hs_pair<kHsTB, true, false> : k_hs_pair<kHsTB, false, false>))
                               : (ecstr ? k_hs_pair<1, true, false> : k_hs_pair<1, false, false>);
-  const int64_t c0 = 16 * pd.hs_nblk;
+  const int64_t c0 = 16 * pd.hs.nblk;
   // p, u, t of a step, and the row slots' accumulators at the end (at most 256 x 16 doubles)
   // of the first and of the last tile (the tiles between them have 256 blocks and one slot)
-  const unsigned ntile = (unsigned)((pd.hs_nblk + 255) / 256);
+  const unsigned ntile = (unsigned)((pd.hs.nblk + 255) / 256);
   int slots = 0;
-  for (int nb : {(int)std::min<int64_t>(256, pd.hs_nblk), (int)(pd.hs_nblk - 256 * (int64_t)(ntile - 1))}) {
+  for (int nb : {(int)std::min<int64_t>(256, pd.hs.nblk), (int)(pd.hs.nblk - 256 * (int64_t)(ntile - 1))}) {
     const int rs = std::min(TB, 256 / nb);
     if (rs > 1) slots = std::max(slots, rs * nb * 16);
   }
   // diff and z of a step and the query's Jacobian
-  const int staged = pd.hs_stage > 0 ? 2 * TB * (int)(D | 1) + 3 * (int)D : 0;
+  const int staged = pd.hs.stage > 0 ? 2 * TB * (int)(D | 1) + 3 * (int)D : 0;
   const size_t lds = sizeof(double) * (size_t)std::max(3 * TB * a.N3P + staged, slots);
-  for (int64_t q0 = 0; q0 < Q; q0 += pd.hs_slab) {
-    const int64_t nq = std::min<int64_t>(pd.hs_slab, Q - q0);
+  for (int64_t q0 = 0; q0 < Q; q0 += pd.hs.slab) {
+    const int64_t nq = std::min<int64_t>(pd.hs.slab, Q - q0);
     a.nq = nq;
-    MLFF_TRY(pred_fd_slab(ctx, R + q0 * N3, nq, !pd.hs_fd));
-    hipLaunchKernelGGL(fn, dim3((unsigned)nq, (unsigned)pd.hs_S, ntile), dim3(kHsThreads), lds, s, a);
+    MLFF_TRY(pred_fd_slab(ctx, R + q0 * N3, nq, !pd.hs.fd));
+    hipLaunchKernelGGL(fn, dim3((unsigned)nq, (unsigned)pd.hs.S, ntile), dim3(kHsThreads), lds, s, a);
     hipLaunchKernelGGL(k_hs_sum, dim3((unsigned)((a.PS + kSumE - 1) / kSumE), (unsigned)nq), dim3(256),
-                       0, s, pd.hs_part, a.PS, nq, pd.hs_S, pd.hs_sum);
+                       0, s, pd.hs.part, a.PS, nq, pd.hs.S, pd.hs.sum);
     hipLaunchKernelGGL(k_hs_fin, dim3((unsigned)((N3 * N3 + 255) / 256), (unsigned)nq), dim3(256), 0, s,
-                       pd.hs_sum, a.PS, pd.Rdq, pd.Rddq, pd.hs_fd ? pd.hs_sum + c0 + 2 : pd.Fd,
-                       pd.hs_fd ? a.PS : D, pd.n, D, c0, pd.std, pd.hs_H);
+                       pd.hs.sum, a.PS, pd.Rdq, pd.Rddq, pd.hs.fd ? pd.hs.sum + c0 + 2 : pd.Fd,
+                       pd.hs.fd ? a.PS : D, pd.n, D, c0, pd.std, pd.hs.H);
     MLFF_HIP(ctx, hipGetLastError());
-    MLFF_HIP(ctx, hipMemcpyAsync(pd.hs_h_out, pd.hs_H, sizeof(double) * nq * N3 * N3,
+    MLFF_HIP(ctx, hipMemcpyAsync(pd.hs.h_out, pd.hs.H, sizeof(double) * nq * N3 * N3,
                                  hipMemcpyDeviceToHost, s));
     // the slab buffers are reused by the next slab: the copy out must have left them
     MLFF_HIP(ctx, hipStreamSynchronize(s));
-    std::memcpy(H_out + q0 * N3 * N3, pd.hs_h_out, sizeof(double) * nq * N3 * N3);
+    std::memcpy(H_out + q0 * N3 * N3, pd.hs.h_out, sizeof(double) * nq * N3 * N3);
   }
   return MLFF_OK;
 }

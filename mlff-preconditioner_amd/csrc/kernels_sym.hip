@@ -1334,9 +1334,8 @@ void launch_symv(const SymPack &sp, const double *v_full, double *P, const int *
   const unsigned G = (unsigned)std::min<int64_t>(sp.dyn, grid);
   static const long long trace_at = sym_knobs().trace_at;
   static long long launches = 0;
-  unsigned long long *tr = nullptr;
-  if (trace_at > 0 && ++launches == trace_at &&
-      hipMalloc(&tr, sizeof(unsigned long long) * kTraceWords * G) == hipSuccess)
+  DevBuf<unsigned long long> tr;
+  if (trace_at > 0 && ++launches == trace_at && tr.alloc((int64_t)kTraceWords * G) == hipSuccess)
     (void)hipMemsetAsync(tr, 0, sizeof(unsigned long long) * kTraceWords * G, s);
   if (sp.gen && sp.rb4)
     hipLaunchKernelGGL((k_symv_dyn<true, 4>), dim3(G), dim3(256), 0, s,
@@ -1350,10 +1349,7 @@ void launch_symv(const SymPack &sp, const double *v_full, double *P, const int *
     hipLaunchKernelGGL(k_symv_dyn<false>, dim3(G), dim3(256), 0, s,
                        sp.tiles, sp.list, v_full, P, sp.Pq, sp.Np, (int)sp.nwhole, (long long)grid,
                        (int)sp.nb, sp.lsub, sp.ticket, status, pg, SymGen{}, tr);
-  if (tr != nullptr) {
-    print_symv_trace(tr, G, grid, sp.wgs, s);
-    (void)hipFree(tr);
-  }
+  if (tr != nullptr) print_symv_trace(tr, G, grid, sp.wgs, s);
 }
 
 void launch_sym_reduce(const SymPack &sp, int64_t n_out, double *y, bool epilogue, double sigma,
@@ -1529,29 +1525,29 @@ static int sym_alloc(mlff_ctx *ctx, const SymPlan &pl, const SymKnobs &kn) {
   hipStream_t s = ctx->stream;
   const int64_t nt = pl.nt, nb = pl.nb, Np = pl.Np, nq = pl.nq;
   if (sp.tiles == nullptr || sp.ntiles != nt || sp.Np != Np || sp.pq_planes != nq) {
-    sym_free(sp);
+    sp = SymPack{};
     if (nt > 0) {
-      MLFF_HIP(ctx, hipMalloc(&sp.tiles, sizeof(double) * nt * B * B));
-      MLFF_HIP(ctx, hipMalloc(&sp.list, sizeof(int2) * nt));
+      MLFF_HIP(ctx, sp.tiles.alloc(nt * B * B));
+      MLFF_HIP(ctx, sp.list.alloc(nt));
     }
-    MLFF_HIP(ctx, hipMalloc(&sp.P, sizeof(double) * nb * Np));
+    MLFF_HIP(ctx, sp.P.alloc(nb * Np));
     MLFF_HIP(ctx, hipMemsetAsync(sp.P, 0, sizeof(double) * nb * Np, s));
-    MLFF_HIP(ctx, hipMalloc(&sp.Pq, sizeof(double) * nq * nb * Np));
+    MLFF_HIP(ctx, sp.Pq.alloc(nq * nb * Np));
     MLFF_HIP(ctx, hipMemsetAsync(sp.Pq, 0, sizeof(double) * nq * nb * Np, s));
     sp.pq_planes = nq;
-    MLFF_HIP(ctx, hipMalloc(&sp.split, (size_t)nb * nb));
-    MLFF_HIP(ctx, hipMalloc(&sp.own, sizeof(int) * (size_t)nb * (nb + 1)));
+    MLFF_HIP(ctx, sp.split.alloc(nb * nb));
+    MLFF_HIP(ctx, sp.own.alloc(nb * (nb + 1)));
     // k_symv_dyn's work counters and the rank reductions' arrival counter (kTicketWords), then
     // the per-CU arrival words of its role rule
     const size_t tw = (kTicketWords + kSymCuWords) * sizeof(unsigned long long);
-    MLFF_HIP(ctx, hipMalloc(&sp.ticket, tw));
+    MLFF_HIP(ctx, sp.ticket.alloc(kTicketWords + kSymCuWords));
     MLFF_HIP(ctx, hipMemsetAsync(sp.ticket, 0, tw, s));
     if (ctx->world > 1) {
       // reduce-scatter operand: rank blocks of blk rows + a tail of p.q shares
       sp.ystride = ctx->blk + round_up(ctx->world, kPad);
       const int64_t ny = (int64_t)ctx->world * sp.ystride;
-      MLFF_HIP(ctx, hipMalloc(&sp.yg, sizeof(double) * ny));
-      MLFF_HIP(ctx, hipMalloc(&sp.yr, sizeof(double) * sp.ystride));
+      MLFF_HIP(ctx, sp.yg.alloc(ny));
+      MLFF_HIP(ctx, sp.yr.alloc(sp.ystride));
       MLFF_HIP(ctx, hipMemsetAsync(sp.yg, 0, sizeof(double) * ny, s));
       MLFF_HIP(ctx, hipMemsetAsync(sp.yr, 0, sizeof(double) * sp.ystride, s));
     }
@@ -1613,10 +1609,9 @@ static int sym_slot_tables(mlff_ctx *ctx, const SymPlan &pl, const SymKnobs &kn)
     std::copy(lists[bi].begin(), lists[bi].end(), plist.begin() + (size_t)bi * sp.pstride);
     plist[(size_t)nb * sp.pstride + bi] = (int)lists[bi].size();
   }
-  if (sp.plist != nullptr) (void)hipFree(sp.plist);
-  sp.plist = nullptr;
+  sp.plist.reset();
   if (ctx->world > 1 && kn.reduce_list) {
-    MLFF_HIP(ctx, hipMalloc(&sp.plist, sizeof(int) * plist.size()));
+    MLFF_HIP(ctx, sp.plist.alloc((int64_t)plist.size()));
     MLFF_HIP(ctx, hipMemcpyAsync(sp.plist, plist.data(), sizeof(int) * plist.size(),
                                  hipMemcpyHostToDevice, s));
   }
@@ -1640,10 +1635,10 @@ static int sym_fill(mlff_ctx *ctx, const SymPlan &pl, bool check_symmetry, bool 
     MLFF_HIP(ctx, hipStreamSynchronize(s));
     return MLFF_OK;
   }
-  unsigned char *dtrans = nullptr;
-  int *dflag = nullptr;
-  MLFF_HIP(ctx, hipMalloc(&dtrans, nt));
-  MLFF_HIP(ctx, hipMalloc(&dflag, sizeof(int)));
+  DevBuf<unsigned char> dtrans;  // both released on every return
+  DevBuf<int> dflag;
+  MLFF_HIP(ctx, dtrans.alloc(nt));
+  MLFF_HIP(ctx, dflag.alloc(1));
   MLFF_HIP(ctx, hipMemcpyAsync(dtrans, pl.trans.data(), nt, hipMemcpyHostToDevice, s));
   MLFF_HIP(ctx, hipMemsetAsync(dflag, 0, sizeof(int), s));
   const int64_t rowbase = (int64_t)ctx->rank * ctx->blk;
@@ -1659,8 +1654,6 @@ static int sym_fill(mlff_ctx *ctx, const SymPlan &pl, bool check_symmetry, bool 
   }
   MLFF_HIP(ctx, hipGetLastError());
   MLFF_HIP(ctx, hipStreamSynchronize(s));
-  (void)hipFree(dtrans);
-  (void)hipFree(dflag);
   if (symmetric_out) *symmetric_out = (mism == 0);
   return MLFF_OK;
 }
@@ -1673,14 +1666,6 @@ int sym_build(mlff_ctx *ctx, bool check_symmetry, bool *symmetric_out) {
   if (int rc = sym_fill(ctx, pl, check_symmetry, symmetric_out); rc != MLFF_OK) return rc;
   ctx->sym.ready = true;
   return MLFF_OK;
-}
-
-void sym_free(SymPack &sp) {
-  for (void *p : {(void *)sp.tiles, (void *)sp.list, (void *)sp.P, (void *)sp.yg, (void *)sp.yr,
-                  (void *)sp.Pq, (void *)sp.split, (void *)sp.ticket, (void *)sp.own,
-                  (void *)sp.plist})
-    if (p) (void)hipFree(p);
-  sp = SymPack{};
 }
 
 }  // namespace mlff

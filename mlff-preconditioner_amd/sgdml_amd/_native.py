@@ -111,6 +111,7 @@ SIGNATURES = {
     "mlff_timing_read_precon": (_int, [_c_ctx, _p_dbl, _p_i64]),
     "mlff_timing_read_comm": (_int, [_c_ctx, _p_dbl, _p_i64]),
     "mlff_device_memory": (_int, [_c_ctx, _p_i64, _p_i64]),
+    "mlff_live_bytes": (_int, [_p_i64]),
 }
 
 _lib = None
@@ -189,6 +190,13 @@ def device_count() -> int:
     n = ctypes.c_int(0)
     rc = lib.mlff_device_count(ctypes.byref(n))
     return n.value if rc == MLFF_OK else 0
+
+
+def live_bytes() -> int:
+    """Bytes of device and pinned memory the library holds in this process (mlff_live_bytes)."""
+    n = ctypes.c_int64(0)
+    check(load_library().mlff_live_bytes(ctypes.byref(n)), None, "mlff_live_bytes")
+    return n.value
 
 
 def comm_unique_id() -> bytes:
