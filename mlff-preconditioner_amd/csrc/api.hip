@@ -348,32 +348,30 @@ int dot_sync(mlff_ctx *ctx, const double *a, const double *b, double *out) {
   return MLFF_OK;
 }
 
-// epoch of the next cluster-apply launch: never 0 (the value of a cleared hand-off slot)
-unsigned next_lr_epoch(mlff_ctx *c) {
-  if (++c->lr_epoch == 0) ++c->lr_epoch;
-  return c->lr_epoch;
-}
-
 double *rho_part(mlff_ctx *c) { return c->part + 0 * kMaxPart; }
 double *pq_part(mlff_ctx *c) { return c->part + 1 * kMaxPart; }
 double *rr_part(mlff_ctx *c) { return c->part + 2 * kMaxPart; }
 
+// Opens a preconditioner build: none until it commits (LowRank::commit); the zeroed panel with
+// its k, the apply's buffers for k rows and the apply's form.
 int alloc_panel(mlff_ctx *ctx, int64_t k) {
-  ctx->tpart_base.reset();
-  ctx->tpart = nullptr;
-  ctx->spec_t = false;
-  MLFF_HIP(ctx, ctx->T.alloc(round_up(k, 8) * ctx->blk));
-  MLFF_HIP(ctx, hipMemsetAsync(ctx->T, 0, sizeof(double) * round_up(k, 8) * ctx->blk, ctx->stream));
-  ctx->tsplit = choose_tsplit(k, ctx->blk);
-  if (const char *e = std::getenv("MLFF_TSPLIT")) ctx->tsplit = std::max(1, std::atoi(e));  // sweeps
-  // [rr partials (kVecGrid) | tpart (k x tsplit)]: on several ranks the end-of-iteration
-  // ||r||^2 reduction and the next iteration's T r reduction share one all-reduce
-  MLFF_HIP(ctx, ctx->tpart_base.alloc(kVecGrid + k * ctx->tsplit));
-  ctx->tpart = ctx->tpart_base + kVecGrid;
-  ctx->zsplit = choose_zsplit(k, ctx->blk);
+  LowRank &lr = ctx->lr;
+  lr.kind = MLFF_PRECON_NONE;
+  lr.k = 0;
+  lr.tpart_base.reset();
+  lr.tpart = nullptr;
+  lr.drop_speculative_t();
+  MLFF_HIP(ctx, lr.T.alloc(round_up(k, 8) * ctx->blk));
+  lr.k = k;
+  MLFF_HIP(ctx, hipMemsetAsync(lr.T, 0, sizeof(double) * round_up(k, 8) * ctx->blk, ctx->stream));
+  lr.tsplit = choose_tsplit(k, ctx->blk);
+  if (const char *e = std::getenv("MLFF_TSPLIT")) lr.tsplit = std::max(1, std::atoi(e));  // sweeps
+  MLFF_HIP(ctx, lr.tpart_base.alloc(kVecGrid + k * lr.tsplit));
+  lr.tpart = lr.tpart_base + kVecGrid;
+  lr.zsplit = choose_zsplit(k, ctx->blk);
   if (const char *e = std::getenv("MLFF_ZSPLIT"))  // sweeps
-    ctx->zsplit = (int)std::min<int64_t>(std::max(1, std::atoi(e)), (k + 15) / 16);
-  MLFF_HIP(ctx, ctx->zpart.alloc(ctx->zsplit * ctx->blk));
+    lr.zsplit = (int)std::min<int64_t>(std::max(1, std::atoi(e)), (k + 15) / 16);
+  MLFF_HIP(ctx, lr.zpart.alloc(lr.zsplit * ctx->blk));
   // one rank, rows that fit a workgroup's registers: the one-pass apply (at >= 7 rows per
   // workgroup its G partial vectors are <= 2/7 of a panel pass) from k = 768, and at any k on
   // short rows (N_loc <= 4096), where the launches it saves dominate the step: ethanol M = 111
@@ -382,32 +380,32 @@ int alloc_panel(mlff_ctx *ctx, int64_t k) {
   // the same either way (52.3 / 52.0 us), and k = 554 keeps the two-pass order its golden
   // fixture's crossings were measured with (profiles/r05/lr_small/).  MLFF_LR_ROWS=0 / 1
   // forces the two-pass / one-pass apply (A/B, tests)
-  ctx->lr_zpart.reset();
-  ctx->lr_slots.reset();
-  ctx->lr_fault.reset();
+  lr.gpart.reset();
+  lr.slots.reset();
+  lr.fault.reset();
+  lr.form = LowRank::kTwoPass;
   const char *lr_env = std::getenv("MLFF_LR_ROWS");
   const bool lr_on = lr_env == nullptr || std::atoi(lr_env) != 0;
-  ctx->lr_rows = ctx->world == 1 && lr_rows_fits(ctx->blk) &&
-                 (lr_env ? lr_on : (k >= 768 || ctx->blk <= 4096));
-  // longer rows: clusters of workgroups share a row (lr_cluster_count of them resident);
-  // worth it from ~4 rows per cluster (the Q partial vectors against the second pass)
-  ctx->lr_cluster = false;
-  if (ctx->world == 1 && !ctx->lr_rows && lr_on && lr_cluster_fits(ctx->blk)) {
-    ctx->lr_q = lr_cluster_count(ctx->blk, ctx->device);
+  if (ctx->world == 1 && lr_rows_fits(ctx->blk) && (lr_env ? lr_on : (k >= 768 || ctx->blk <= 4096))) {
+    lr.form = LowRank::kRows;
+  } else if (ctx->world == 1 && lr_on && lr_cluster_fits(ctx->blk)) {
+    // longer rows: clusters of workgroups share a row (lr_cluster_count of them resident);
+    // worth it from ~4 rows per cluster (the Q partial vectors against the second pass)
+    lr.q = lr_cluster_count(ctx->blk, ctx->device);
     if (const char *e = std::getenv("MLFF_LR_CLUSTERS"))  // A/B: fewer clusters
-      ctx->lr_q = std::min(ctx->lr_q, std::max(1, std::atoi(e)));
-    ctx->lr_cluster = ctx->lr_q >= 1 && k >= 4 * (int64_t)ctx->lr_q;
+      lr.q = std::min(lr.q, std::max(1, std::atoi(e)));
+    if (lr.q >= 1 && k >= 4 * (int64_t)lr.q) lr.form = LowRank::kCluster;
   }
-  if (ctx->lr_rows)
-    MLFF_HIP(ctx, ctx->lr_zpart.alloc(lr_rows_groups(k) * ctx->blk));
-  if (ctx->lr_cluster) {
+  if (lr.form == LowRank::kRows)
+    MLFF_HIP(ctx, lr.gpart.alloc(lr_rows_groups(k) * ctx->blk));
+  if (lr.form == LowRank::kCluster) {
     const size_t ns = (size_t)k * lr_cluster_members(ctx->blk) * 2;
-    MLFF_HIP(ctx, ctx->lr_zpart.alloc(ctx->lr_q * ctx->blk));
-    MLFF_HIP(ctx, ctx->lr_slots.alloc((int64_t)ns));
-    MLFF_HIP(ctx, hipMemsetAsync(ctx->lr_slots, 0, sizeof(unsigned long long) * ns, ctx->stream));
-    MLFF_HIP(ctx, ctx->lr_fault.alloc(1));
-    MLFF_HIP(ctx, hipMemsetAsync(ctx->lr_fault, 0, sizeof(int), ctx->stream));
-    ctx->lr_epoch = 0;
+    MLFF_HIP(ctx, lr.gpart.alloc(lr.q * ctx->blk));
+    MLFF_HIP(ctx, lr.slots.alloc((int64_t)ns));
+    MLFF_HIP(ctx, hipMemsetAsync(lr.slots, 0, sizeof(unsigned long long) * ns, ctx->stream));
+    MLFF_HIP(ctx, lr.fault.alloc(1));
+    MLFF_HIP(ctx, hipMemsetAsync(lr.fault, 0, sizeof(int), ctx->stream));
+    lr.epoch = 0;
   }
   return MLFF_OK;
 }
@@ -883,6 +881,49 @@ void mark_end(mlff_ctx *ctx, std::vector<GemvMark> *marks, size_t i0, long long 
   }
 }
 
+// The halves of the two-pass apply.  lowrank_tr: tpart = T r, summed over the ranks unless the
+// caller's own collective carries it (reduce = false: the ranks iteration's merged all-reduce);
+// lowrank_z: z = sigma_p / lam (r - T^T tpart) with the rho partials r . z (rho may be null).
+int lowrank_tr(mlff_ctx *ctx, const double *r, const int *status, StopFold fold = StopFold{},
+               bool reduce = true) {
+  const LowRank &lr = ctx->lr;
+  launch_gemv_split(lr.T, ctx->blk, lr.k, ctx->blk, lr.tsplit, r, lr.tpart, status, ctx->stream, fold);
+  if (reduce) MLFF_TRY(allreduce(ctx, lr.tpart, (size_t)(lr.k * lr.tsplit)));
+  return MLFF_OK;
+}
+
+void lowrank_z(mlff_ctx *ctx, const double *r, double *z, double *rho, const int *status,
+               StopFold fold = StopFold{}) {
+  const LowRank &lr = ctx->lr;
+  launch_precon_z(lr.T, ctx->blk, lr.k, lr.tsplit, lr.tpart, r, z, ctx->nrows, lr.sigma_p,
+                  1.0 / ctx->lam, rho, status, ctx->stream, lr.zpart, lr.zsplit, fold);
+}
+
+// z = sigma_p / lam (r - T^T T r) and the rho partials r . z (rho may be null) in the form the
+// build chose (the one-pass forms: one rank only).  status gates the kernels (null: ungated),
+// fold / xf ride in the apply's first kernel, fault is the cluster form's time-out word (ST_FAULT).
+int lowrank_apply(mlff_ctx *ctx, const double *r, double *z, double *rho, const int *status,
+                  int *fault, StopFold fold = StopFold{}, XrFold xf = XrFold{}) {
+  LowRank &lr = ctx->lr;
+  hipStream_t s = ctx->stream;
+  const double lam_inv = 1.0 / ctx->lam;
+  if (ctx->exact_sums) {  // measurement anchor: two double-double passes, stop test and rho separately
+    if (fold.st != nullptr) launch_stoptest(fold.rr_part, fold.st, fold.trace, fold.it, s);
+    launch_dd_lowrank(lr.T, ctx->blk, lr.k, r, z, ctx->nrows, lr.sigma_p, lam_inv, lr.tpart, status, s);
+    if (rho != nullptr) launch_dot_part(r, z, ctx->nrows, rho, status, s);
+  } else if (lr.form == LowRank::kRows) {
+    launch_lr_apply_rows(lr.T, ctx->blk, lr.k, r, z, ctx->nrows, lr.sigma_p, lam_inv, rho, status, s,
+                         lr.gpart, fold, xf);
+  } else if (lr.form == LowRank::kCluster) {
+    launch_lr_apply_cluster(lr.T, ctx->blk, lr.k, lr.q, r, z, ctx->nrows, lr.sigma_p, lam_inv, rho,
+                            status, s, lr.gpart, lr.slots, lr.next_epoch(), fault, fold);
+  } else {
+    MLFF_TRY(lowrank_tr(ctx, r, status, fold));
+    lowrank_z(ctx, r, z, rho, status);
+  }
+  return MLFF_OK;
+}
+
 // One PCG iteration on several ranks: three collectives instead of five:
 //   allgather(z_g | rho partials)  -> rho and the whole p on every rank
 //   [symmetric tiles] reduce-scatter(K p partial rows | p.q shares) -> q rows and p.q
@@ -896,22 +937,19 @@ int launch_iteration_ranks(mlff_ctx *ctx, long long it, std::vector<GemvMark> *m
   const int *status = &ctx->st->status;
   double *p_loc = ctx->p_full + (int64_t)ctx->rank * ctx->blk;
   double *zg = ctx->gb + (int64_t)ctx->rank * ctx->gstride;  // this rank's gather block
-  const bool lowrank = ctx->precon_kind != MLFF_PRECON_NONE;
-  double *rrp = lowrank ? ctx->tpart_base : rr_part(ctx);
+  LowRank &lr = ctx->lr;
+  const bool lowrank = lr.active();
+  double *rrp = lowrank ? lr.tpart_base : rr_part(ctx);
   StopFold fold;  // stop test of iteration it - 1 in this iteration's first kernel
   if (fold_in) fold = StopFold{rrp, ctx->st, ctx->trace, it - 1};
   if (lowrank) {
-    if (!ctx->spec_t) {
-      launch_gemv_split(ctx->T, ctx->blk, ctx->k, ctx->blk, ctx->tsplit, ctx->r, ctx->tpart, status, s,
-                        fold);
+    if (!lr.spec_t) {
+      MLFF_TRY(lowrank_tr(ctx, ctx->r, status, fold));
       fold = StopFold{};
-      MLFF_TRY(allreduce(ctx, ctx->tpart, (size_t)(ctx->k * ctx->tsplit)));
     }
     // the low-rank apply: T r (issued at the end of the previous iteration, kind 3) + z here
     const size_t pm = mark_begin(ctx, marks);
-    launch_precon_z(ctx->T, ctx->blk, ctx->k, ctx->tsplit, ctx->tpart, ctx->r, zg, ctx->nrows,
-                    ctx->sigma_p, 1.0 / ctx->lam, zg + ctx->blk, status, s, ctx->zpart, ctx->zsplit,
-                    fold);
+    lowrank_z(ctx, ctx->r, zg, zg + ctx->blk, status, fold);
     mark_end(ctx, marks, pm, it, 1);
   } else {
     launch_copy_dot(ctx->r, ctx->nrows, zg, zg + ctx->blk, status, s, fold);
@@ -940,28 +978,26 @@ int launch_iteration_ranks(mlff_ctx *ctx, long long it, std::vector<GemvMark> *m
     MLFF_TRY(comm_reduce_scatter(ctx, sp.yg, sp.yr, (size_t)sp.ystride));
     mark_end(ctx, marks, c0, it, 2);
     launch_update_xr_shares(ctx->x, ctx->r, p_loc, sp.yr, sp.yr + ctx->blk, ctx->world, ctx->nrows,
-                            ctx->sigma_K, ctx->lam, lowrank ? ctx->tpart_base : rr_part(ctx),
-                            ctx->st, status, s);
+                            ctx->sigma_K, ctx->lam, rrp, ctx->st, status, s);
   } else {
     MLFF_TRY(launch_operator(ctx, ctx->p_full, ctx->q, p_loc, status, pq_part(ctx)));
     mark_end(ctx, marks, e0, it);
     c0 = mark_begin(ctx, marks);
     MLFF_TRY(allreduce(ctx, pq_part(ctx), kVecGrid));
     mark_end(ctx, marks, c0, it, 2);
-    launch_update_xr(ctx->x, ctx->r, p_loc, ctx->q, ctx->nrows, pq_part(ctx),
-                     lowrank ? ctx->tpart_base : rr_part(ctx), ctx->st, status, s);
+    launch_update_xr(ctx->x, ctx->r, p_loc, ctx->q, ctx->nrows, pq_part(ctx), rrp, ctx->st, status, s);
   }
   if (lowrank) {
     // the T r half of iteration it + 1's apply: bracketed with that iteration (its
     // z half, kind 1) so a sampled apply is always timed whole
     ctx->timing.sample = (it + 1) % ctx->timing.every == 0;
     const size_t tm = mark_begin(ctx, marks);
-    launch_gemv_split(ctx->T, ctx->blk, ctx->k, ctx->blk, ctx->tsplit, ctx->r, ctx->tpart, status, s);
+    MLFF_TRY(lowrank_tr(ctx, ctx->r, status, StopFold{}, false));
     mark_end(ctx, marks, tm, it, 3);
     c0 = mark_begin(ctx, marks);
-    MLFF_TRY(allreduce(ctx, ctx->tpart_base, (size_t)(kVecGrid + ctx->k * ctx->tsplit)));
+    MLFF_TRY(allreduce(ctx, lr.tpart_base, (size_t)(kVecGrid + lr.k * lr.tsplit)));
     mark_end(ctx, marks, c0, it, 2);
-    ctx->spec_t = true;
+    lr.spec_t = true;
   } else {
     c0 = mark_begin(ctx, marks);
     MLFF_TRY(allreduce(ctx, rrp, kVecGrid));
@@ -983,7 +1019,7 @@ int launch_iteration(mlff_ctx *ctx, long long it, std::vector<GemvMark> *marks, 
   hipStream_t s = ctx->stream;
   const int *status = &ctx->st->status;
   double *p_loc = ctx->p_full + (int64_t)ctx->rank * ctx->blk;
-  const bool lowrank = ctx->precon_kind != MLFF_PRECON_NONE;
+  const bool lowrank = ctx->lr.active();
   StopFold fold;
   if (fold_in) fold = StopFold{rr_part(ctx), ctx->st, ctx->trace, it - 1};
   // matrix-free operator (default form): p = z + beta p formed inside the operator kernels;
@@ -991,7 +1027,7 @@ int launch_iteration(mlff_ctx *ctx, long long it, std::vector<GemvMark> *marks, 
   // iteration's apply (x, r, rr partials written by k_lr_fin) and its stop test into the
   // operator's first kernel: 4 launches per iteration instead of 6
   const bool fuse_p = ctx->use_mf && mf_can_fuse_p(ctx);
-  const bool fuse_xr = fuse_p && lowrank && ctx->lr_rows && ctx->fuse_xr;
+  const bool fuse_xr = fuse_p && lowrank && ctx->lr.form == LowRank::kRows && ctx->fuse_xr;
   XrFold xf;
   StopFold fold_op;
   if (fuse_xr && fold_in) {  // iteration it - 1 left its x, r update to this iteration
@@ -1009,25 +1045,7 @@ int launch_iteration(mlff_ctx *ctx, long long it, std::vector<GemvMark> *marks, 
   const double *zsrc;
   if (lowrank) {
     const size_t pm = mark_begin(ctx, marks);
-    if (ctx->exact_sums) {  // measurement anchor: two double-double passes, rho separately
-      if (fold.st != nullptr) launch_stoptest(rr_part(ctx), ctx->st, ctx->trace, it - 1, s);
-      launch_dd_lowrank(ctx->T, ctx->blk, ctx->k, ctx->r, ctx->z, ctx->nrows, ctx->sigma_p,
-                        1.0 / ctx->lam, ctx->tpart, status, s);
-      launch_dot_part(ctx->r, ctx->z, ctx->nrows, rho_part(ctx), status, s);
-    } else if (ctx->lr_rows) {
-      launch_lr_apply_rows(ctx->T, ctx->blk, ctx->k, ctx->r, zout, ctx->nrows, ctx->sigma_p,
-                           1.0 / ctx->lam, rhoout, status, s, ctx->lr_zpart, fold, xf);
-    } else if (ctx->lr_cluster) {
-      launch_lr_apply_cluster(ctx->T, ctx->blk, ctx->k, ctx->lr_q, ctx->r, zout, ctx->nrows,
-                              ctx->sigma_p, 1.0 / ctx->lam, rhoout, status, s,
-                              ctx->lr_zpart, ctx->lr_slots, next_lr_epoch(ctx), &ctx->st->status,
-                              fold);
-    } else {
-      launch_gemv_split(ctx->T, ctx->blk, ctx->k, ctx->blk, ctx->tsplit, ctx->r, ctx->tpart, status,
-                        s, fold);
-      launch_precon_z(ctx->T, ctx->blk, ctx->k, ctx->tsplit, ctx->tpart, ctx->r, zout, ctx->nrows,
-                      ctx->sigma_p, 1.0 / ctx->lam, rhoout, status, s, ctx->zpart, ctx->zsplit);
-    }
+    MLFF_TRY(lowrank_apply(ctx, ctx->r, zout, rhoout, status, &ctx->st->status, fold, xf));
     mark_end(ctx, marks, pm, it, 1);
     zsrc = zout;
   } else {
@@ -1780,8 +1798,8 @@ int mlff_get_diag(mlff_ctx *ctx, double *diag_local) {
 int mlff_precon_none(mlff_ctx *ctx) {
   MLFF_API_BEGIN
   MLFF_ENTER(ctx);
-  ctx->precon_kind = MLFF_PRECON_NONE;
-  ctx->k = 0;
+  ctx->lr.kind = MLFF_PRECON_NONE;  // the panel's buffers stay until the next build
+  ctx->lr.k = 0;
   return MLFF_OK;
   MLFF_API_END(ctx)
 }
@@ -1794,18 +1812,16 @@ int mlff_precon_pivchol(mlff_ctx *ctx, int64_t k, int build_woodbury, int64_t *i
   if (k < 1 || k > ctx->N || k > 65536)
     return set_error(ctx, MLFF_ERR_ARG, "pivoted Cholesky rank k must satisfy 1 <= k <= min(N, 65536)");
   const auto t0 = std::chrono::steady_clock::now();
-  ctx->precon_kind = MLFF_PRECON_NONE;
   MLFF_TRY(alloc_panel(ctx, k));
   MLFF_HIP(ctx, ctx->prow.alloc(k + 1));
   MLFF_TRY(pivoted_cholesky(ctx, k, index_columns_out));
-  ctx->k = k;  // without Woodbury the panel holds L^T (mlff_precon_get_panel), unused by PCG
+  // without Woodbury the panel holds L^T (mlff_precon_get_panel), unused by PCG
   ctx->piv_woodbury_s = 0.0;
   if (build_woodbury) {
     const auto tw = std::chrono::steady_clock::now();
-    MLFF_TRY(woodbury_inplace(ctx, ctx->T, k));
+    MLFF_TRY(woodbury_inplace(ctx, ctx->lr.T, k));
     ctx->piv_woodbury_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count();
-    ctx->precon_kind = MLFF_PRECON_PIVCHOL;
-    ctx->sigma_p = 1.0;
+    ctx->lr.commit(MLFF_PRECON_PIVCHOL, 1.0);
   }
   MLFF_HIP(ctx, hipStreamSynchronize(ctx->stream));
   if (seconds_out)
@@ -1835,12 +1851,10 @@ int mlff_precon_nystrom(mlff_ctx *ctx, const int64_t *idx, int64_t k, int varian
   if (variant != 0 && variant != 1) return set_error(ctx, MLFF_ERR_ARG, "variant must be 0 or 1");
   MLFF_TRY(check_idx(ctx, idx, k));
   const auto t0 = std::chrono::steady_clock::now();
-  ctx->precon_kind = MLFF_PRECON_NONE;
   MLFF_TRY(alloc_panel(ctx, k));
-  MLFF_TRY(nystrom_panel(ctx, idx, k, variant, ctx->lam, ctx->T));
-  ctx->precon_kind = variant == 0 ? MLFF_PRECON_NYSTROM : MLFF_PRECON_NYSTROM_SB;
-  ctx->k = k;
-  ctx->sigma_p = -1.0;  // _P_vec returns (B^T B v - v)/lam; _sb returns -(v - P^T P v)/lam
+  MLFF_TRY(nystrom_panel(ctx, idx, k, variant, ctx->lam, ctx->lr.T));
+  // _P_vec returns (B^T B v - v)/lam; _sb returns -(v - P^T P v)/lam
+  ctx->lr.commit(variant == 0 ? MLFF_PRECON_NYSTROM : MLFF_PRECON_NYSTROM_SB, -1.0);
   if (seconds_out)
     *seconds_out = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   return MLFF_OK;
@@ -1853,16 +1867,13 @@ int mlff_precon_lowrank(mlff_ctx *ctx, const double *Lt_local, int64_t k) {
   MLFF_TRY(require_operator(ctx));
   if (k < 1 || k > ctx->N || (Lt_local == nullptr && ctx->nrows > 0))
     return set_error(ctx, MLFF_ERR_ARG, "lowrank: bad factor");
-  ctx->precon_kind = MLFF_PRECON_NONE;
   MLFF_TRY(alloc_panel(ctx, k));
   if (ctx->nrows > 0)
-    MLFF_HIP(ctx, hipMemcpy2DAsync(ctx->T, sizeof(double) * ctx->blk, Lt_local,
+    MLFF_HIP(ctx, hipMemcpy2DAsync(ctx->lr.T, sizeof(double) * ctx->blk, Lt_local,
                                    sizeof(double) * ctx->nrows, sizeof(double) * ctx->nrows, k,
                                    hipMemcpyHostToDevice, ctx->stream));
-  MLFF_TRY(woodbury_inplace(ctx, ctx->T, k));
-  ctx->precon_kind = MLFF_PRECON_LOWRANK;
-  ctx->k = k;
-  ctx->sigma_p = 1.0;
+  MLFF_TRY(woodbury_inplace(ctx, ctx->lr.T, k));
+  ctx->lr.commit(MLFF_PRECON_LOWRANK, 1.0);
   return MLFF_OK;
   MLFF_API_END(ctx)
 }
@@ -1879,14 +1890,11 @@ int mlff_precon_eig(mlff_ctx *ctx, int64_t k, int mask_mode, int64_t dim_i, int 
     MLFF_TRY(require_operator(ctx));
   }
   if (k < 1 || k > ctx->N) return set_error(ctx, MLFF_ERR_ARG, "eig: need 1 <= k <= N");
-  ctx->precon_kind = MLFF_PRECON_NONE;
   MLFF_TRY(alloc_panel(ctx, k));
-  MLFF_TRY(eig_lowrank(ctx, k, mask_mode, dim_i, ctx->T, evals_out, rowlev_out));
+  MLFF_TRY(eig_lowrank(ctx, k, mask_mode, dim_i, ctx->lr.T, evals_out, rowlev_out));
   if (build_woodbury) {
-    MLFF_TRY(woodbury_inplace(ctx, ctx->T, k));
-    ctx->precon_kind = MLFF_PRECON_EIG;
-    ctx->k = k;
-    ctx->sigma_p = 1.0;
+    MLFF_TRY(woodbury_inplace(ctx, ctx->lr.T, k));
+    ctx->lr.commit(MLFF_PRECON_EIG, 1.0);
   }
   return MLFF_OK;
   MLFF_API_END(ctx)
@@ -1904,8 +1912,8 @@ int mlff_eig_info(mlff_ctx *ctx, int *converged_out, double *rel_resid_out) {
 int mlff_precon_info(mlff_ctx *ctx, int *kind_out, int64_t *k_out) {
   MLFF_API_BEGIN
   MLFF_ENTER(ctx);
-  if (kind_out) *kind_out = ctx->precon_kind;
-  if (k_out) *k_out = ctx->k;
+  if (kind_out) *kind_out = ctx->lr.kind;
+  if (k_out) *k_out = ctx->lr.k;
   return MLFF_OK;
   MLFF_API_END(ctx)
 }
@@ -1913,19 +1921,8 @@ int mlff_precon_info(mlff_ctx *ctx, int *kind_out, int64_t *k_out) {
 int mlff_precon_apply_traffic(mlff_ctx *ctx, int *one_pass_out, double *bytes_out) {
   MLFF_API_BEGIN
   MLFF_ENTER(ctx);
-  const double N = (double)ctx->blk, n = (double)ctx->nrows, k = (double)ctx->k;
-  const bool one = ctx->precon_kind != MLFF_PRECON_NONE && (ctx->lr_rows || ctx->lr_cluster);
-  if (one_pass_out) *one_pass_out = one ? (ctx->lr_cluster ? 2 : 1) : 0;
-  if (bytes_out) {
-    if (ctx->precon_kind == MLFF_PRECON_NONE)
-      *bytes_out = 0.0;
-    else if (one)
-      *bytes_out = 8.0 * k * N +
-                   16.0 * (double)(ctx->lr_cluster ? ctx->lr_q : lr_rows_groups(ctx->k)) * N +
-                   24.0 * n;
-    else
-      *bytes_out = 16.0 * k * N + 24.0 * n;
-  }
+  if (one_pass_out) *one_pass_out = ctx->lr.apply_form();
+  if (bytes_out) *bytes_out = ctx->lr.apply_bytes(ctx->blk, ctx->nrows);
   return MLFF_OK;
   MLFF_API_END(ctx)
 }
@@ -1942,52 +1939,25 @@ int mlff_precon_apply(mlff_ctx *ctx, const double *r_local, double *z_local) {
   MLFF_HIP(ctx, hipMemsetAsync(rd, 0, sizeof(double) * ctx->blk, s));
   if (ctx->nrows > 0)
     MLFF_HIP(ctx, hipMemcpyAsync(rd, r_local, sizeof(double) * ctx->nrows, hipMemcpyHostToDevice, s));
-  if (ctx->precon_kind == MLFF_PRECON_NONE) {
+  LowRank &lr = ctx->lr;
+  if (!lr.active()) {
     MLFF_HIP(ctx, hipMemcpyAsync(zd, rd, sizeof(double) * ctx->blk, hipMemcpyDeviceToDevice, s));
   } else {
-    ctx->spec_t = false;  // tpart is reused below
-    if (ctx->exact_sums) {  // the measurement anchor's apply (kernels_dd.hip)
-      launch_dd_lowrank(ctx->T, ctx->blk, ctx->k, rd, zd, ctx->nrows, ctx->sigma_p, 1.0 / ctx->lam,
-                        ctx->tpart, nullptr, s);
+    lr.drop_speculative_t();  // tpart is reused below
+    const bool cluster = !ctx->exact_sums && lr.form == LowRank::kCluster;
+    if (cluster) MLFF_HIP(ctx, hipMemsetAsync(lr.fault, 0, sizeof(int), s));
+    MLFF_TRY(lowrank_apply(ctx, rd, zd, nullptr, nullptr, lr.fault));
+    if (cluster) {
       MLFF_HIP(ctx, hipGetLastError());
-      if (ctx->nrows > 0)
-        MLFF_HIP(ctx, hipMemcpyAsync(z_local, zd, sizeof(double) * ctx->nrows, hipMemcpyDeviceToHost, s));
+      int fault = 0;
+      MLFF_HIP(ctx, hipMemcpyAsync(&fault, lr.fault, sizeof(int), hipMemcpyDeviceToHost, s));
       MLFF_HIP(ctx, hipStreamSynchronize(s));
-      return MLFF_OK;
-    }
-    if (ctx->lr_rows || ctx->lr_cluster) {
-      if (ctx->lr_rows) {
-        launch_lr_apply_rows(ctx->T, ctx->blk, ctx->k, rd, zd, ctx->nrows, ctx->sigma_p,
-                             1.0 / ctx->lam, nullptr, nullptr, s, ctx->lr_zpart);
-      } else {
-        MLFF_HIP(ctx, hipMemsetAsync(ctx->lr_fault, 0, sizeof(int), s));
-        launch_lr_apply_cluster(ctx->T, ctx->blk, ctx->k, ctx->lr_q, rd, zd, ctx->nrows,
-                                ctx->sigma_p, 1.0 / ctx->lam, nullptr, nullptr, s, ctx->lr_zpart,
-                                ctx->lr_slots, next_lr_epoch(ctx), ctx->lr_fault);
+      if (fault != 0) {  // hand-offs timed out (members not all resident): two passes
+        lr.demote_cluster();
+        MLFF_TRY(lowrank_tr(ctx, rd, nullptr));
+        lowrank_z(ctx, rd, zd, nullptr, nullptr);
       }
-      MLFF_HIP(ctx, hipGetLastError());
-      if (ctx->lr_cluster) {
-        int fault = 0;
-        MLFF_HIP(ctx, hipMemcpyAsync(&fault, ctx->lr_fault, sizeof(int), hipMemcpyDeviceToHost, s));
-        MLFF_HIP(ctx, hipStreamSynchronize(s));
-        if (fault != 0) {  // hand-offs timed out (members not all resident): two passes
-          ctx->lr_cluster = false;
-          ctx->lr_fallbacks += 1;
-          launch_gemv_split(ctx->T, ctx->blk, ctx->k, ctx->blk, ctx->tsplit, rd, ctx->tpart, nullptr, s);
-          launch_precon_z(ctx->T, ctx->blk, ctx->k, ctx->tsplit, ctx->tpart, rd, zd, ctx->nrows,
-                          ctx->sigma_p, 1.0 / ctx->lam, nullptr, nullptr, s, ctx->zpart, ctx->zsplit);
-          MLFF_HIP(ctx, hipGetLastError());
-        }
-      }
-      if (ctx->nrows > 0)
-        MLFF_HIP(ctx, hipMemcpyAsync(z_local, zd, sizeof(double) * ctx->nrows, hipMemcpyDeviceToHost, s));
-      MLFF_HIP(ctx, hipStreamSynchronize(s));
-      return MLFF_OK;
     }
-    launch_gemv_split(ctx->T, ctx->blk, ctx->k, ctx->blk, ctx->tsplit, rd, ctx->tpart, nullptr, s);
-    MLFF_TRY(allreduce(ctx, ctx->tpart, (size_t)(ctx->k * ctx->tsplit)));
-    launch_precon_z(ctx->T, ctx->blk, ctx->k, ctx->tsplit, ctx->tpart, rd, zd, ctx->nrows,
-                    ctx->sigma_p, 1.0 / ctx->lam, nullptr, nullptr, s, ctx->zpart, ctx->zsplit);
   }
   MLFF_HIP(ctx, hipGetLastError());
   if (ctx->nrows > 0)
@@ -2000,11 +1970,11 @@ int mlff_precon_apply(mlff_ctx *ctx, const double *r_local, double *z_local) {
 int mlff_precon_get_panel(mlff_ctx *ctx, double *T_local, int64_t ld_out) {
   MLFF_API_BEGIN
   MLFF_ENTER(ctx);
-  if (ctx->T == nullptr || ctx->k < 1) return set_error(ctx, MLFF_ERR_STATE, "no low-rank panel");
+  if (ctx->lr.T == nullptr || ctx->lr.k < 1) return set_error(ctx, MLFF_ERR_STATE, "no low-rank panel");
   if (T_local == nullptr || ld_out < ctx->nrows) return set_error(ctx, MLFF_ERR_ARG, "bad output");
   if (ctx->nrows > 0)
-    MLFF_HIP(ctx, hipMemcpy2DAsync(T_local, sizeof(double) * ld_out, ctx->T, sizeof(double) * ctx->blk,
-                                   sizeof(double) * ctx->nrows, ctx->k, hipMemcpyDeviceToHost, ctx->stream));
+    MLFF_HIP(ctx, hipMemcpy2DAsync(T_local, sizeof(double) * ld_out, ctx->lr.T, sizeof(double) * ctx->blk,
+                                   sizeof(double) * ctx->nrows, ctx->lr.k, hipMemcpyDeviceToHost, ctx->stream));
   MLFF_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MLFF_OK;
   MLFF_API_END(ctx)
@@ -2097,7 +2067,7 @@ int mlff_pcg_start(mlff_ctx *ctx, const double *b_local, const double *x0_local,
   MLFF_HIP(ctx, hipMemcpyAsync(ctx->trace, &r0, sizeof(double), hipMemcpyHostToDevice, s));
   MLFF_HIP(ctx, hipStreamSynchronize(s));
   *ctx->h_st = h;
-  ctx->spec_t = false;
+  ctx->lr.drop_speculative_t();
   ctx->tol = tol;
   ctx->bnorm = bnorm;
   ctx->pcg_done = 0;
@@ -2135,13 +2105,12 @@ int mlff_pcg_run(mlff_ctx *ctx, int64_t n_iter, int64_t chunk, int *status_out) 
     }
     MLFF_HIP(ctx, hipGetLastError());
     MLFF_TRY(poll_state(ctx));
-    if (ctx->h_st->status == ST_FAULT && ctx->lr_cluster) {
+    if (ctx->h_st->status == ST_FAULT && ctx->lr.form == LowRank::kCluster) {
       // the cluster apply could not complete its hand-offs (its workgroups were not all
       // resident, e.g. another process's kernels held CUs): nothing of iteration iters + 1
       // was written past its (idempotent) stop test, so the solve continues from there on
       // the two-pass apply
-      ctx->lr_cluster = false;
-      ctx->lr_fallbacks += 1;
+      ctx->lr.demote_cluster();
       ctx->h_st->status = ST_RUNNING;
       MLFF_HIP(ctx, hipMemsetAsync(&ctx->st->status, 0, sizeof(int), s));  // ST_RUNNING
     }
@@ -2172,7 +2141,7 @@ int mlff_pcg_run(mlff_ctx *ctx, int64_t n_iter, int64_t chunk, int *status_out) 
     while (ctx->h_st->status == ST_RECHECK) {
       MLFF_TRY(do_recheck(ctx));
       MLFF_TRY(poll_state(ctx));
-      ctx->spec_t = false;  // r was recomputed: the speculative T r is stale
+      ctx->lr.drop_speculative_t();  // r was recomputed
     }
     ctx->pcg_done = ctx->h_st->iters;
   }

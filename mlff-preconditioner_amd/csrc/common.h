@@ -296,6 +296,53 @@ struct PredData {
   } hs;
 };
 
+// Low-rank preconditioner z = sigma_p / lam (r - T^T T r): the panel, the form of its apply and
+// that form's work buffers.  alloc_panel (api.hip) opens a build: kind NONE, k recorded with the
+// panel, so T has round_up(k, 8) rows whether or not the build goes on to commit().
+int lr_rows_groups(int64_t k);  // kernels_vec.hip, declared with the launchers below
+struct LowRank {
+  // the apply, as mlff_precon_apply_traffic reports it: T r then T^T t; one pass, a workgroup's
+  // registers hold a row (launch_lr_apply_rows) or a cluster's do (launch_lr_apply_cluster)
+  enum Form : int { kTwoPass = 0, kRows = 1, kCluster = 2 };
+  int kind = MLFF_PRECON_NONE;  // MLFF_PRECON_*: NONE until a build commits
+  int64_t k = 0;                // rows of T in use (0: mlff_precon_none)
+  DevBuf<double> T;             // k x blk (row stride blk)
+  double sigma_p = 1.0;
+  Form form = kTwoPass;         // chosen per build; one rank only for the one-pass forms
+  int tsplit = 1;               // column splits of the T GEMV
+  int zsplit = 1;               // row splits of the T^T t GEMV
+  DevBuf<double> zpart;         // zsplit x blk partials
+  int q = 0;                    // kCluster: its clusters
+  DevBuf<double> gpart;         // one pass: lr_rows_groups(k) (or q) x blk partials
+  DevBuf<unsigned long long> slots;  // cluster hand-off granules (k x C x 2)
+  unsigned epoch = 0;           // per cluster launch, never 0 in a launch
+  DevBuf<int> fault;            // ST_FAULT when a cluster hand-off timed out (precon_apply)
+  int fallbacks = 0;            // cluster applies that timed out and fell back to two passes
+  // [rr partials (kVecGrid) | tpart (k x tsplit)]: on several ranks the end-of-iteration
+  // ||r||^2 reduction and the next iteration's T r reduction share one all-reduce
+  DevBuf<double> tpart_base;
+  double *tpart = nullptr;      // view: tpart_base + kVecGrid
+  bool spec_t = false;          // tpart already holds T r of the current r (merged collective)
+  bool active() const { return kind != MLFF_PRECON_NONE; }
+  void commit(int kind_, double sigma) { kind = kind_; sigma_p = sigma; }
+  Form apply_form() const { return active() ? form : kTwoPass; }
+  // bytes one apply moves, the counterpart of operator_bytes: the panel once or twice, the
+  // one-pass forms' partial vectors written and read, r read and z written and read
+  double apply_bytes(int64_t blk, int64_t nrows) const {
+    const double N = (double)blk, n = (double)nrows, kd = (double)k;
+    if (!active()) return 0.0;
+    if (form == kTwoPass) return 16.0 * kd * N + 24.0 * n;
+    return 8.0 * kd * N + 16.0 * (double)(form == kCluster ? q : lr_rows_groups(k)) * N + 24.0 * n;
+  }
+  // epoch of the next cluster-apply launch: never 0 (the value of a cleared hand-off slot)
+  unsigned next_epoch() { return ++epoch != 0 ? epoch : ++epoch; }
+  // a cluster hand-off timed out (the members were not all resident): two passes from here on
+  void demote_cluster() { form = kTwoPass; fallbacks += 1; }
+  // tpart no longer holds T r of the solver's r: the buffer was reallocated or reused for
+  // another vector, or r was set anew (a solve's start, the true-residual recheck)
+  void drop_speculative_t() { spec_t = false; }
+};
+
 // Synthetic RBF kernel source (tools/utils.py:173-187): the points, scaled by 1 / length
 // scale, stay on the device and every consumer evaluates K from them -- the symmetric
 // tiles are generated directly, columns / the diagonal / requested rows on demand -- so no
@@ -588,8 +635,8 @@ struct mlff_ctx {
   bool has_matrix = false;
   double sigma_K = 1.0, lam = 0.0;
   bool has_operator = false;
-  bool K_symmetric = false;
-  bool use_E_cstr = false;   // mlff_set_energy_constraints: sGDML systems of size 3 n M + M  // known symmetric by construction (generated / assembled)
+  bool K_symmetric = false;  // known symmetric by construction (generated / assembled)
+  bool use_E_cstr = false;   // mlff_set_energy_constraints: sGDML systems of size 3 n M + M
   int storage = MLFF_STORAGE_AUTO;  // requested operator storage
   bool use_sym = false;             // resolved: symmetric tiles in use
   bool use_mf = false;              // resolved: matrix-free sGDML operator in use
@@ -612,15 +659,7 @@ struct mlff_ctx {
   int64_t pcg_done = 0;   // iterations known complete on the host side
   double tol = 0.0, bnorm = 0.0;
 
-  // preconditioner
-  int precon_kind = MLFF_PRECON_NONE;
-  int64_t k = 0;
-  mlff::DevBuf<double> T; // k x blk (row stride blk)
-  double sigma_p = 1.0;   // z = sigma_p * (r - T^T T r) / lam
-  int tsplit = 1;         // column splits of the T GEMV
-  int zsplit = 1;         // row splits of the T^T t GEMV
-  mlff::DevBuf<double> zpart;  // zsplit x blk partials
-  bool lr_rows = false;        // one-pass low-rank apply (launch_lr_apply_rows), one rank
+  mlff::LowRank lr;       // the preconditioner: z = sigma_p * (r - T^T T r) / lam
   // CG vector updates folded into the matrix-free nanotube iteration; read from
   // MLFF_FUSE_P / MLFF_FUSE_XR (=0: separate launches) when the context is created
   bool fuse_p = true, fuse_xr = true;
@@ -639,20 +678,10 @@ struct mlff_ctx {
   // exact-sum anchor (MLFF_EXACT_SUMS=1, kernels_dd.hip): dense-row operator and two-pass low-rank
   // apply with double-double dot products rounded once per entry; one rank; measurement only
   bool exact_sums = false;
-  bool lr_cluster = false;     // the same for long rows (launch_lr_apply_cluster)
-  int lr_q = 0;                // its clusters
-  mlff::DevBuf<double> lr_zpart;  // lr_rows_groups(k) (or lr_q) x blk partials
-  mlff::DevBuf<unsigned long long> lr_slots;  // cluster hand-off granules (k x C x 2)
-  unsigned lr_epoch = 0;       // per cluster launch, never 0 in a launch
-  mlff::DevBuf<int> lr_fault;  // ST_FAULT when a cluster hand-off timed out (precon_apply)
-  int lr_fallbacks = 0;        // cluster applies that timed out and fell back to two passes
-  double last_lo_eig = 0.0;
+  double last_lo_eig = 0.0;  // lo_eig of the last _cho_factor_stable (cho_factor_stable)
   bool cho_flipped = false;  // a cho_factor_stable retried upward after a noisy lo > 0
   bool eig_converged = true;   // last truncated eigensolve met kEigTol (kernels_eig.hip)
-  double eig_rel_resid = 0.0;  // its worst Ritz residual / |theta_0|    // lo_eig of the last _cho_factor_stable (cho_factor_stable)
-  double *tpart = nullptr;       // view: tpart_base + kVecGrid
-  mlff::DevBuf<double> tpart_base;
-  bool spec_t = false;           // tpart already holds T r of the current r (merged collective)
+  double eig_rel_resid = 0.0;  // its worst Ritz residual / |theta_0|
 
   // pivoted Cholesky scratch
   mlff::DevBuf<int64_t> perm;  // global permutation (replicated)

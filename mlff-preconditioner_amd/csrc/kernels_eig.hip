@@ -586,7 +586,7 @@ int spectrum(mlff_ctx *ctx, bool preconditioned, double *eig_out) {
   const int64_t n = ctx->N, blk = ctx->blk;
   if (ctx->world > 1) return set_error(ctx, MLFF_ERR_ARG, "spectrum: one rank only");
   if (n > 46340) return set_error(ctx, MLFF_ERR_ARG, "spectrum: N too large for a dense N x N");
-  if (preconditioned && ctx->precon_kind == MLFF_PRECON_NONE) preconditioned = false;
+  if (preconditioned && !ctx->lr.active()) preconditioned = false;
   MLFF_TRY(operator_prepare(ctx));
   ScratchScope scope(ctx);
   double *Y = nullptr, *A = nullptr, *V = nullptr, *x = nullptr, *rq = nullptr;
@@ -607,9 +607,9 @@ int spectrum(mlff_ctx *ctx, bool preconditioned, double *eig_out) {
     double *R = Y;  // Y is free now (n x n fits in its n x blk)
     MLFF_HIP(ctx, hipMemcpyAsync(R, A, sizeof(double) * n * n, hipMemcpyDeviceToDevice, s));
     MLFF_TRY(potrf_lower(ctx, R, n));
-    const int64_t k = ctx->k;
+    const int64_t k = ctx->lr.k;
     double *X = x;  // k x n
-    launch_gemm(false, false, k, n, n, 1.0, ctx->T, blk, R, n, 0.0, X, n, s);
+    launch_gemm(false, false, k, n, n, 1.0, ctx->lr.T, blk, R, n, 0.0, X, n, s);
     launch_gemm(true, false, n, n, n, 1.0 / ctx->lam, R, n, R, n, 0.0, A, n, s);
     launch_gemm(true, false, n, n, k, -1.0 / ctx->lam, X, n, X, n, 1.0, A, n, s);
     hipLaunchKernelGGL(k_symmetrize, dim3(grid1(n * n)), dim3(256), 0, s, A, (int)n);
@@ -619,7 +619,7 @@ int spectrum(mlff_ctx *ctx, bool preconditioned, double *eig_out) {
   std::vector<double> d(n);
   MLFF_HIP(ctx, hipMemcpyAsync(d.data(), rq, sizeof(double) * n, hipMemcpyDeviceToHost, s));
   MLFF_HIP(ctx, hipStreamSynchronize(s));
-  const double sg = preconditioned ? ctx->sigma_p : 1.0;
+  const double sg = preconditioned ? ctx->lr.sigma_p : 1.0;
   for (int64_t i = 0; i < n; ++i) d[i] *= sg;
   std::sort(d.begin(), d.end(), [](double a, double b) { return a > b; });
   std::copy(d.begin(), d.end(), eig_out);

@@ -1025,7 +1025,7 @@ int pivoted_cholesky(mlff_ctx *ctx, int64_t k, int64_t *index_columns_out) {
   }
   int64_t spec_m0 = -1;  // start of the current speculative block (-1: none)
   MLFF_HIP(ctx, hipMemsetAsync(ctx->pivflag, 0, sizeof(int) * blk, s));
-  MLFF_HIP(ctx, hipMemsetAsync(ctx->T, 0, sizeof(double) * round_up(k, 8) * blk, s));
+  MLFF_HIP(ctx, hipMemsetAsync(ctx->lr.T, 0, sizeof(double) * round_up(k, 8) * blk, s));
   MLFF_HIP(ctx, hipMemsetAsync(&ctx->st->pivot_err, 0, sizeof(int), s));
   // per-column build times (incomplete_cholesky.py:48-80 records time_cholesky[m] for every
   // column; tools/create_data.py:117-148 compares the first 20 with the rest): a device
@@ -1087,7 +1087,7 @@ int pivoted_cholesky(mlff_ctx *ctx, int64_t k, int64_t *index_columns_out) {
     pa.nrows = nrows;
     pa.blk = blk;
     pa.rows_per = ctx->rows_per;
-    pa.Lt = ctx->T;
+    pa.Lt = ctx->lr.T;
     pa.dwork = ctx->dwork;
     pa.pivflag = ctx->pivflag;
     pa.perm = ctx->perm;
@@ -1147,8 +1147,8 @@ int pivoted_cholesky(mlff_ctx *ctx, int64_t k, int64_t *index_columns_out) {
           hipLaunchKernelGGL(k_spec_top_merge, dim3(kSpecMergeWG), dim3(256), 0, s, (const double *)cv,
                              (const long long *)ci, Cspec);
           hipLaunchKernelGGL(k_spec_gather, dim3((unsigned)std::min<int64_t>((m * kSpecC + 255) / 256, 4096)),
-                             dim3(256), 0, s, ctx->T, blk, m, Cspec, Aspec);
-          MLFF_TRY(gemm_splitk(ctx, true, false, kSpecC, blk, m, Aspec, kSpecC, ctx->T, blk, Gspec, blk));
+                             dim3(256), 0, s, ctx->lr.T, blk, m, Cspec, Aspec);
+          MLFF_TRY(gemm_splitk(ctx, true, false, kSpecC, blk, m, Aspec, kSpecC, ctx->lr.T, blk, Gspec, blk));
           if (colbuf != nullptr) {  // the candidates' columns, the steps' hits read them
             launch_sgdml_columns(mf.Rdd, mf.M, mf.n, mf.D, mf.i0, mf.pi_d, mf.piinv_d, mf.n_perms,
                                  mf.uvk, ctx->row0, nrows, Cspec, kSpecC, ctx->st, ctx->sigma_K,
@@ -1246,8 +1246,8 @@ int pivoted_cholesky(mlff_ctx *ctx, int64_t k, int64_t *index_columns_out) {
       hipLaunchKernelGGL(k_spec_top_merge, dim3(kSpecMergeWG), dim3(256), 0, s, (const double *)cv,
                          (const long long *)ci, Cspec);
       hipLaunchKernelGGL(k_spec_gather, dim3((unsigned)std::min<int64_t>((m * kSpecC + 255) / 256, 4096)),
-                         dim3(256), 0, s, ctx->T, blk, m, Cspec, Aspec);
-      MLFF_TRY(gemm_splitk(ctx, true, false, kSpecC, blk, m, Aspec, kSpecC, ctx->T, blk, Gspec, blk));
+                         dim3(256), 0, s, ctx->lr.T, blk, m, Cspec, Aspec);
+      MLFF_TRY(gemm_splitk(ctx, true, false, kSpecC, blk, m, Aspec, kSpecC, ctx->lr.T, blk, Gspec, blk));
     }
     const bool multi = ctx->world > 1;
     if (multi) {
@@ -1259,7 +1259,7 @@ int pivoted_cholesky(mlff_ctx *ctx, int64_t k, int64_t *index_columns_out) {
     hipLaunchKernelGGL(k_piv_finalize, dim3(1), dim3(256), 0, s, wins, ctx->world,
                        multi ? nullptr : (const double *)pv,
                        multi ? nullptr : (const long long *)pp, npc, ctx->perm, m, ctx->row0,
-                       nrows, ctx->T, blk, ctx->pivflag, multi ? ctx->prow : nullptr, xunit,
+                       nrows, ctx->lr.T, blk, ctx->pivflag, multi ? ctx->prow : nullptr, xunit,
                        ctx->rows_per, blk, ctx->st, iperm, spec_m0 >= 0 ? Cspec : nullptr, hit);
     if (multi && m > 0) MLFF_TRY(comm_allreduce(ctx, ctx->prow, (size_t)m));
     if (rbfcols)
@@ -1274,14 +1274,14 @@ int pivoted_cholesky(mlff_ctx *ctx, int64_t k, int64_t *index_columns_out) {
     // panel's leading rows (up to 128 MB) are read with default-policy loads so they stay in
     // the MALL from one step to the next
     if (ks > 0)
-      launch_colgemv_part(ctx->T, blk, m, ctx->prow, 1, m, ks, part, nullptr, s, StopFold{},
+      launch_colgemv_part(ctx->lr.T, blk, m, ctx->prow, 1, m, ks, part, nullptr, s, StopFold{},
                           panel_cached_rows(m, blk),
                           multi ? nullptr : (const long long *)&ctx->st->m_pi,
                           in_spec ? hit : nullptr, in_spec ? spec_m0 : 0);
     if (gcol > 0)
       hipLaunchKernelGGL(k_piv_fin, dim3(gcol), dim3(256), 0, s, ctx->K, ctx->ld, ctx->sigma_K,
                        (const double *)colbuf, ctx->rows_per, blk, nrows, m, part, ks, blk,
-                       ctx->T, blk, ctx->pivflag, ctx->dwork, ctx->st, xunit, iperm, ctx->row0, N,
+                       ctx->lr.T, blk, ctx->pivflag, ctx->dwork, ctx->st, xunit, iperm, ctx->row0, N,
                        pv, pp, (const double *)Gspec, in_spec ? (const int *)hit : nullptr);
     else if (mfcols && !colpath)
       hipLaunchKernelGGL(k_unit_pivot, dim3(1), dim3(64), 0, s, ctx->xg, ctx->rows_per, blk,

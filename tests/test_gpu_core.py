@@ -304,6 +304,46 @@ def test_call_order_and_argument_errors(sg):
         assert res.info == 0
 
 
+def test_panel_rows_and_k_agree(sg):
+    """k is recorded where the panel is allocated: a build that allocates a panel and does not
+    commit a preconditioner (precon_eig without its Woodbury step) reports the new panel's k
+    with kind NONE and hands out that panel -- 8 rows after a 40-row build, the bits of a fresh
+    context's (the one-rank eigen build is a function of its inputs: hash-seeded start panel).
+    precon_none forgets the panel; a 40-row build after the 8-row one is whole again.
+    n = 513 is no multiple of 64 (padded tail of the rows), 8 is one round_up(k, 8) row group."""
+    from sgdml_amd import _native as nat
+
+    n, lam = 513, 0.5
+    X, _ = _rbf(n)
+    r = np.random.default_rng(513).standard_normal(n)
+
+    def solver():
+        s = sg.KernelSolver(n)
+        s.gen_rbf(X, length_scale=0.2)
+        s.set_operator(1.0, lam)
+        return s
+
+    with solver() as s:
+        s.precon_eig(8, build_woodbury=False)
+        fresh = s.precon_panel()
+    with solver() as s:
+        s.precon_pivchol(40)
+        s.precon_eig(8, build_woodbury=False)
+        assert s.precon_info() == (nat.PRECON_NONE, 8)
+        T8 = s.precon_panel()
+        assert T8.shape == (8, 513)
+        assert np.array_equal(T8, fresh)
+        s.precon_none()
+        with pytest.raises(RuntimeError, match="no low-rank panel"):
+            s.precon_panel()
+        s.precon_pivchol(40)
+        assert s.precon_info() == (nat.PRECON_PIVCHOL, 40)
+        T = s.precon_panel()
+        z = s.precon_apply(r)
+    zref = (r - T.T @ (T @ r)) / lam
+    assert np.linalg.norm(z - zref) <= 1e-12 * np.linalg.norm(zref)
+
+
 @pytest.mark.parametrize("n,k,clusters", [(1000, 3, 0), (1000, 800, 0), (5000, 1031, 0),
                                           (11000, 900, 0), (15540, 2701, 0),
                                           (20000, 400, 0), (40000, 301, 0), (40000, 301, 3),
