@@ -943,396 +943,443 @@ __global__ __launch_bounds__(256) void k_perm_from_iperm(const int64_t *__restri
 }
 
 // the persistent form applies: one rank, the dense rows or the sGDML single-column path, a panel
-// short enough for its pivot row to sit in LDS, and MLFF_PIVCHOL_PERSIST not 0
-static bool persist_grid(int64_t k, int64_t nrw, int *G_out) {
+// short enough for its pivot row to sit in LDS, and MLFF_PIVCHOL_PERSIST not 0.  Its grid, or 0
+static int persist_grid(int64_t k, int64_t nrw) {
   const char *e0 = std::getenv("MLFF_PIVCHOL_PERSIST");  // read per build: 0 = launch sequence
-  if ((e0 != nullptr && std::atoi(e0) == 0) || k > 12288) return false;
+  if ((e0 != nullptr && std::atoi(e0) == 0) || k > 12288) return 0;
   int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return false;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
   hipDeviceProp_t prop;
-  if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
+  if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return 0;
   cus = prop.multiProcessorCount;
   int per = 0;
   const size_t shm = sizeof(double) * (size_t)std::max<int64_t>(k, 8);
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, reinterpret_cast<const void *>(k_piv_persist<true>),
                                                    256, shm) != hipSuccess || per < 1)
-    return false;
+    return 0;
   // every row wave is one wave of the grid (its rows' state lives in registers): G >= nrw / 4;
   // all of the grid resident at once (one workgroup per CU)
   const int64_t need = (nrw + 3) / 4, cap = std::min<int64_t>(256, cus);
-  if (need > cap) return false;
+  if (need > cap) return 0;
   // fewer workgroups poll faster (configs[1], 63 needed: 64 / 128 / 256 -> 15.8 / 16.5 / 17.8 us
   // per step, profiles/r06/pivchol/)
   int64_t G = std::max<int64_t>(need, std::min<int64_t>(cap, 64));
   if (const char *e = std::getenv("MLFF_PIV_G")) G = std::max<int64_t>(need, std::min<int64_t>(cap, std::atoi(e)));
-  *G_out = (int)G;
-  return true;
+  return (int)G;
 }
 
-int pivoted_cholesky(mlff_ctx *ctx, int64_t k, int64_t *index_columns_out) {
-  hipStream_t s = ctx->stream;
-  const int64_t N = ctx->N, nrows = ctx->nrows, blk = ctx->blk;
-  const int np = (int)std::min<int64_t>(256, std::max<int64_t>(1, (N + 1023) / 1024));
-  const unsigned gcol = (unsigned)std::min<int64_t>((nrows + 255) / 256, 1024);
-  ScratchScope scope(ctx);
-  double *pv = nullptr, *wins = nullptr;
-  long long *pp = nullptr;
-  int64_t *iperm = nullptr;
-  const int npart = std::max<int>(np, (int)gcol);
-  MLFF_TRY(scratch_alloc(ctx, &pv, npart));
-  MLFF_TRY(scratch_alloc(ctx, &pp, npart));
-  MLFF_TRY(scratch_alloc(ctx, &wins, 2 * ctx->world));
-  MLFF_TRY(scratch_alloc(ctx, &iperm, N));
-  // init: perm = iperm = arange(N), dwork = diag(S), pivflag = 0, Lt = 0
-  std::vector<int64_t> hperm(N);
-  for (int64_t i = 0; i < N; ++i) hperm[i] = i;
-  MLFF_HIP(ctx, hipMemcpyAsync(ctx->perm, hperm.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
-  MLFF_HIP(ctx, hipMemcpyAsync(iperm, hperm.data(), sizeof(int64_t) * N, hipMemcpyHostToDevice, s));
+// What the two forms of a build share: the sizes, the column source, the form, and the scratch of
+// the pivot search and of the speculative blocks.  piv_setup fills it and starts the build.
+struct PivBuild {
+  int64_t k = 0, N = 0, nrows = 0, blk = 0;
+  int np = 0;          // workgroups of the position scan (k_piv_argmax)
+  unsigned gcol = 0;   // workgroups of the launch sequence's finisher (k_piv_fin)
+  int npart = 0;       // entries of pv / pp: what the form's partial writers need
+  int kmax_split = 0;  // slices of part
   // column sources: the dense rows; the RBF points (k_rbf_cols); the matrix-free sGDML
   // operator -- its single-column path (one training point's pair records, k_sgdml_col)
   // when the table exists, else K_op e_{m_pi} through the whole operator
-  const bool rbfcols = !ctx->has_matrix && ctx->rbf.ready;
-  const bool mfcols = !ctx->has_matrix && !rbfcols;
-  const bool colpath = rbfcols || (mfcols && (ctx->mf.uvk != nullptr || ctx->nrows == 0));
-  double *colbuf = nullptr, *part = nullptr;
-  if (!ctx->has_matrix) {
-    MLFF_TRY(operator_diag(ctx, ctx->dwork));
-    MLFF_TRY(scratch_alloc(ctx, &colbuf, blk));
-    MLFF_HIP(ctx, hipMemsetAsync(ctx->xg, 0, sizeof(double) * ctx->ld, s));
-  } else {
-    launch_diag_of(ctx->K, ctx->ld, nrows, ctx->row0, ctx->rows_per, blk, ctx->sigma_K, ctx->dwork, s);
-  }
-  const int kmax_split = choose_ksplit(k, blk);
-  MLFF_TRY(scratch_alloc(ctx, &part, kmax_split * blk));
+  bool rbfcols = false, mfcols = false, colpath = false;
+  // the persistent form (k_piv_persist): its grid (0: the launch sequence) and its row waves
+  // (64 dense rows, or 64 rows of a query point)
+  int Gp = 0;
+  int64_t nrw = 0;
+  double *pv = nullptr, *wins = nullptr, *part = nullptr;
+  long long *pp = nullptr;
+  int64_t *iperm = nullptr;
+  std::vector<int64_t> hperm;  // arange(N): the host source of two uploads, kept until the build ends
   // speculative blocks (one rank; MLFF_PIVCHOL_SPEC=0 disables for A/B)
-  static const bool spec_env = [] {
-    const char *e = std::getenv("MLFF_PIVCHOL_SPEC");
-    return e == nullptr || e[0] != '0';
-  }();
-  const bool spec = spec_env && ctx->world == 1 && k > kSpecMin + kSpecB &&
-                    nrows > (int64_t)kSpecGroups * kSpecPer;
+  bool spec = false;
   double *Gspec = nullptr, *Aspec = nullptr, *cv = nullptr;
   long long *ci = nullptr;
   int64_t *Cspec = nullptr;
   int *hit = nullptr;
-  if (spec) {
-    MLFF_TRY(scratch_alloc(ctx, &Gspec, (size_t)kSpecC * blk));
-    MLFF_TRY(scratch_alloc(ctx, &Aspec, (size_t)k * kSpecC));
-    MLFF_TRY(scratch_alloc(ctx, &cv, (size_t)kSpecGroups * kSpecPer));
-    MLFF_TRY(scratch_alloc(ctx, &ci, (size_t)kSpecGroups * kSpecPer));
-    MLFF_TRY(scratch_alloc(ctx, &Cspec, (size_t)kSpecC));
-    MLFF_TRY(scratch_alloc(ctx, &hit, 1));
-  }
-  int64_t spec_m0 = -1;  // start of the current speculative block (-1: none)
-  MLFF_HIP(ctx, hipMemsetAsync(ctx->pivflag, 0, sizeof(int) * blk, s));
-  MLFF_HIP(ctx, hipMemsetAsync(ctx->lr.T, 0, sizeof(double) * round_up(k, 8) * blk, s));
-  MLFF_HIP(ctx, hipMemsetAsync(&ctx->st->pivot_err, 0, sizeof(int), s));
-  // per-column build times (incomplete_cholesky.py:48-80 records time_cholesky[m] for every
-  // column; tools/create_data.py:117-148 compares the first 20 with the rest): a device
-  // event every kStampEvery columns, the segment's time split evenly over its columns
-  constexpr int64_t kStampEvery = 4;
-  std::vector<hipEvent_t> stamps;
-  stamps.reserve((size_t)(k / kStampEvery + 2));
-  auto stamp = [&]() {
-    hipEvent_t e = nullptr;
-    if (hipEventCreateWithFlags(&e, timing_event_flags()) == hipSuccess) {
-      hipEventRecord(e, s);
-      stamps.push_back(e);
-    }
-  };
-  std::vector<int64_t> stamp_col;  // the column each stamp precedes
-  stamp_col.reserve(stamps.capacity());
-  auto stamp_at = [&](int64_t m) {
-    stamp();
-    if (stamp_col.size() < stamps.size()) stamp_col.push_back(m);
-  };
-  // the persistent form (k_piv_persist): one launch per speculative block
-  unsigned long long *step_clock = nullptr;  // its per-step clocks (split each launch's time)
-  int Gp = 0;
-  int64_t nrw = (nrows + 63) / 64;  // row waves: 64 dense rows, or 64 rows of a query point
-  if (!ctx->has_matrix && mfcols && ctx->mf.uvk != nullptr) {
+};
+
+// classify the column source, choose the form, take the shared scratch; on the stream:
+// perm = iperm = arange(N), dwork = diag(S), pivflag = 0, Lt = 0, pivot_err = 0
+static int piv_setup(mlff_ctx *ctx, int64_t k, PivBuild *out) {
+  hipStream_t s = ctx->stream;
+  PivBuild &b = *out;
+  b.k = k;
+  b.N = ctx->N;
+  b.nrows = ctx->nrows;
+  b.blk = ctx->blk;
+  b.np = (int)std::min<int64_t>(256, std::max<int64_t>(1, (b.N + 1023) / 1024));
+  b.gcol = (unsigned)std::min<int64_t>((b.nrows + 255) / 256, 1024);
+  b.kmax_split = choose_ksplit(k, b.blk);
+  b.rbfcols = !ctx->has_matrix && ctx->rbf.ready;
+  b.mfcols = !ctx->has_matrix && !b.rbfcols;
+  b.colpath = b.rbfcols || (b.mfcols && (ctx->mf.uvk != nullptr || ctx->nrows == 0));
+  const bool sgcol = b.mfcols && ctx->mf.uvk != nullptr;
+  b.nrw = (b.nrows + 63) / 64;
+  if (sgcol) {
     const int64_t n3 = 3 * (int64_t)ctx->mf.n;
-    nrw = ((nrows + n3 - 1) / n3) * ((n3 + kColRows - 1) / kColRows);  // one rank: row0 = 0
+    b.nrw = ((b.nrows + n3 - 1) / n3) * ((n3 + kColRows - 1) / kColRows);  // one rank: row0 = 0
   }
-  const bool persist = ctx->world == 1 && nrows > 0 && !rbfcols && !ctx->piv_persist_off &&
-                       (ctx->has_matrix || (mfcols && ctx->mf.uvk != nullptr)) &&
-                       persist_grid(k, nrw, &Gp);
-  if (persist) {
-    const bool sg = !ctx->has_matrix;
-    const MfData &mf = ctx->mf;
-    long long *pr = nullptr;
-    double *pv2 = nullptr;
-    long long *pp2 = nullptr, *pr2 = nullptr;
-    unsigned long long *slots = nullptr, *flags = nullptr;
-    MLFF_TRY(scratch_alloc(ctx, &pr, npart));
-    MLFF_TRY(scratch_alloc(ctx, &pv2, std::max(npart, Gp)));
-    MLFF_TRY(scratch_alloc(ctx, &pp2, std::max(npart, Gp)));
-    MLFF_TRY(scratch_alloc(ctx, &pr2, std::max(npart, Gp)));
-    MLFF_TRY(scratch_alloc(ctx, &slots, (size_t)2 * Gp * kSlot));
-    MLFF_TRY(scratch_alloc(ctx, &flags, (size_t)Gp));
-    unsigned long long *cands = nullptr;
-    MLFF_TRY(scratch_alloc(ctx, &cands, (size_t)2 * 2 * kSpecC));
-    MLFF_HIP(ctx, hipMemsetAsync(cands, 0, sizeof(unsigned long long) * 2 * 2 * kSpecC, s));
-    double *colbuf = nullptr;  // the candidates' columns (sGDML path, speculative blocks)
-    if (sg && spec) MLFF_TRY(scratch_alloc(ctx, &colbuf, (size_t)kSpecC * blk));
-    MLFF_HIP(ctx, hipMemsetAsync(slots, 0, sizeof(unsigned long long) * 2 * Gp * kSlot, s));
-    MLFF_HIP(ctx, hipMemsetAsync(flags, 0, sizeof(unsigned long long) * Gp, s));
-    if (npart < Gp) {  // the partial buffers hold G entries
-      MLFF_TRY(scratch_alloc(ctx, &pv, Gp));
-      MLFF_TRY(scratch_alloc(ctx, &pp, Gp));
-      MLFF_TRY(scratch_alloc(ctx, &pr, Gp));
-    }
-    PersistArgs pa{};
-    pa.N = N;
-    pa.nrows = nrows;
-    pa.blk = blk;
-    pa.rows_per = ctx->rows_per;
-    pa.Lt = ctx->lr.T;
-    pa.dwork = ctx->dwork;
-    pa.pivflag = ctx->pivflag;
-    pa.perm = ctx->perm;
-    pa.iperm = iperm;
-    pa.st = ctx->st;
-    pa.K = sg ? nullptr : ctx->K;
-    pa.ld = ctx->ld;
-    pa.sigma = ctx->sigma_K;
-    if (sg) {
-      pa.Rdd = mf.Rdd;
-      pa.M = mf.M;
-      pa.n = mf.n;
-      pa.D = mf.D;
-      pa.i0 = mf.i0;
-      pa.pi = mf.pi_d;
-      pa.piinv = mf.piinv_d;
-      pa.n_perms = mf.n_perms;
-      pa.uvk = mf.uvk;
-      pa.chunks = (3 * mf.n + kColRows - 1) / kColRows;
-    }
-    pa.nrw = (int)nrw;
-    pa.part = part;
-    pa.kmax_split = kmax_split;
-    pa.Cspec = Cspec;
-    pa.Gspec = Gspec;
-    pa.cands = cands;
-    pa.colbuf = nullptr;
-    pa.mute = -1;
-    pa.trace = nullptr;
-    MLFF_TRY(scratch_alloc(ctx, &pa.step_clock, (size_t)2 * k));
-    MLFF_HIP(ctx, hipMemsetAsync(pa.step_clock, 0, sizeof(unsigned long long) * 2 * k, s));
-    step_clock = pa.step_clock;
-    const bool want_trace = std::getenv("MLFF_PIV_TRACE") != nullptr;
-    if (want_trace) {
-      MLFF_TRY(scratch_alloc(ctx, &pa.trace, (size_t)k * Gp * 4));
-      MLFF_HIP(ctx, hipMemsetAsync(pa.trace, 0, sizeof(unsigned long long) * k * Gp * 4, s));
-    }
-    if (const char *e = std::getenv("MLFF_PIV_MUTE")) pa.mute = std::atoi(e);
-    const size_t shm = sizeof(double) * (size_t)std::max<int64_t>(k, 8);
-    hipLaunchKernelGGL(k_piv_argmax, dim3(np), dim3(256), 0, s, ctx->dwork, ctx->perm, N, (int64_t)0,
-                       ctx->row0, nrows, pv, pp);
-    const double *pin = pv;
-    const long long *ppin = pp, *prin = nullptr;
-    int npc = np;
-    bool flip = false;
-    stamp_at(0);
-    for (int64_t m = 0; m < k;) {
-      int64_t m_end = k;
-      pa.spec_m0 = -1;
-      if (spec) {
-        if (m < kSpecMin) {
-          m_end = std::min<int64_t>(k, kSpecMin);
-          pa.colbuf = nullptr;
-        } else {
-          hipLaunchKernelGGL(k_spec_top_part, dim3(kSpecGroups), dim3(256), 0, s, ctx->dwork,
-                             ctx->pivflag, nrows, cv, ci);
-          hipLaunchKernelGGL(k_spec_top_merge, dim3(kSpecMergeWG), dim3(256), 0, s, (const double *)cv,
-                             (const long long *)ci, Cspec);
-          hipLaunchKernelGGL(k_spec_gather, dim3((unsigned)std::min<int64_t>((m * kSpecC + 255) / 256, 4096)),
-                             dim3(256), 0, s, ctx->lr.T, blk, m, Cspec, Aspec);
-          MLFF_TRY(gemm_splitk(ctx, true, false, kSpecC, blk, m, Aspec, kSpecC, ctx->lr.T, blk, Gspec, blk));
-          if (colbuf != nullptr) {  // the candidates' columns, the steps' hits read them
-            launch_sgdml_columns(mf.Rdd, mf.M, mf.n, mf.D, mf.i0, mf.pi_d, mf.piinv_d, mf.n_perms,
-                                 mf.uvk, ctx->row0, nrows, Cspec, kSpecC, ctx->st, ctx->sigma_K,
-                                 colbuf, blk, s);
-            pa.colbuf = colbuf;
-          }
-          pa.spec_m0 = m;
-          m_end = std::min<int64_t>(k, m + kSpecB);
-        }
-      }
-      pa.pv_in = pin;
-      pa.pp_in = ppin;
-      pa.pr_in = prin;
-      pa.npc = npc;
-      pa.pv_out = flip ? pv : pv2;
-      pa.pp_out = flip ? pp : pp2;
-      pa.pr_out = flip ? pr : pr2;
-      pa.slots = slots;
-      pa.flags = flags;
-      pa.m_begin = m;
-      pa.m_end = m_end;
-      if (sg)
-        hipLaunchKernelGGL(k_piv_persist<true>, dim3((unsigned)Gp), dim3(256), shm, s, pa);
-      else
-        hipLaunchKernelGGL(k_piv_persist<false>, dim3((unsigned)Gp), dim3(256), shm, s, pa);
-      MLFF_HIP(ctx, hipGetLastError());
-      pin = pa.pv_out;
-      ppin = pa.pp_out;
-      prin = pa.pr_out;
-      npc = Gp;
-      flip = !flip;
-      m = m_end;
-      stamp_at(m);
-    }
-    hipLaunchKernelGGL(k_perm_from_iperm, dim3((unsigned)std::min<int64_t>((N + 255) / 256, 1024)),
-                       dim3(256), 0, s, (const int64_t *)iperm, N, ctx->perm);
-    if (want_trace) {  // per step: the medians over workgroups of each phase, and the step time
-      std::vector<unsigned long long> tr((size_t)k * Gp * 4);
-      MLFF_HIP(ctx, hipMemcpyAsync(tr.data(), pa.trace, sizeof(unsigned long long) * tr.size(),
-                                   hipMemcpyDeviceToHost, s));
-      MLFF_HIP(ctx, hipStreamSynchronize(s));
-      double acc[4] = {0, 0, 0, 0};
-      double slow_sum = 0.0, fast_sum = 0.0;  // steps with / without a grid-wide Schur GEMV
-      int64_t cnt = 0, slow = 0;
-      for (int64_t m = 1; m + 1 < k; ++m) {
-        const unsigned long long *a0 = &tr[(size_t)m * Gp * 4], *a1 = &tr[(size_t)(m + 1) * Gp * 4];
-        if (a0[0] == 0 || a1[0] == 0 || a0[3] == 0) continue;  // launch boundaries
-        std::vector<double> ph[4];
-        for (int g = 0; g < Gp; ++g) {
-          const unsigned long long *e = a0 + 4 * g, *f = a1 + 4 * g;
-          ph[0].push_back(10.0 * (double)(e[1] - e[0]));
-          ph[1].push_back(e[2] > e[1] ? 10.0 * (double)(e[2] - e[1]) : 0.0);
-          ph[2].push_back(10.0 * (double)(e[3] - (e[2] > e[1] ? e[2] : e[1])));
-          ph[3].push_back(10.0 * (double)(f[0] - e[0]));
-        }
-        for (int q = 0; q < 4; ++q) {
-          std::nth_element(ph[q].begin(), ph[q].begin() + Gp / 2, ph[q].end());
-          acc[q] += ph[q][Gp / 2];
-        }
-        if (ph[0][Gp / 2] > 20000.0) {
-          ++slow;
-          slow_sum += ph[3][Gp / 2];
-        } else {
-          fast_sum += ph[3][Gp / 2];
-        }
-        ++cnt;
-      }
-      if (cnt > 0)
-        std::fprintf(stderr, "[piv trace] G=%d steps=%lld median ns: winner+stage+miss %.0f, rows %.0f, "
-                     "publish %.0f, step %.0f\n", Gp, (long long)cnt, acc[0] / cnt, acc[1] / cnt,
-                     acc[2] / cnt, acc[3] / cnt);
-      if (cnt > 0)
-        std::fprintf(stderr, "[piv trace] %lld steps > 20 us before the rows (misses): %.2f ms; "
-                     "the other %lld: %.2f ms\n", (long long)slow, 1e-6 * slow_sum,
-                     (long long)(cnt - slow), 1e-6 * fast_sum);
-    }
+  if (ctx->world == 1 && b.nrows > 0 && !b.rbfcols && !ctx->piv_persist_off && (ctx->has_matrix || sgcol))
+    b.Gp = persist_grid(k, b.nrw);
+  // the position scan's partials, then each step's: the persistent grid's, or k_piv_fin's
+  b.npart = std::max<int>(b.np, b.Gp > 0 ? b.Gp : (int)b.gcol);
+  MLFF_TRY(scratch_alloc(ctx, &b.pv, b.npart));
+  MLFF_TRY(scratch_alloc(ctx, &b.pp, b.npart));
+  MLFF_TRY(scratch_alloc(ctx, &b.wins, 2 * ctx->world));
+  MLFF_TRY(scratch_alloc(ctx, &b.iperm, b.N));
+  MLFF_TRY(scratch_alloc(ctx, &b.part, b.kmax_split * b.blk));
+  static const bool spec_env = [] {
+    const char *e = std::getenv("MLFF_PIVCHOL_SPEC");
+    return e == nullptr || e[0] != '0';
+  }();
+  b.spec = spec_env && ctx->world == 1 && k > kSpecMin + kSpecB &&
+           b.nrows > (int64_t)kSpecGroups * kSpecPer;
+  if (b.spec) {
+    MLFF_TRY(scratch_alloc(ctx, &b.Gspec, (size_t)kSpecC * b.blk));
+    MLFF_TRY(scratch_alloc(ctx, &b.Aspec, (size_t)k * kSpecC));
+    MLFF_TRY(scratch_alloc(ctx, &b.cv, (size_t)kSpecGroups * kSpecPer));
+    MLFF_TRY(scratch_alloc(ctx, &b.ci, (size_t)kSpecGroups * kSpecPer));
+    MLFF_TRY(scratch_alloc(ctx, &b.Cspec, (size_t)kSpecC));
+    MLFF_TRY(scratch_alloc(ctx, &b.hit, 1));
+  }
+  b.hperm.resize(b.N);
+  for (int64_t i = 0; i < b.N; ++i) b.hperm[i] = i;
+  MLFF_HIP(ctx, hipMemcpyAsync(ctx->perm, b.hperm.data(), sizeof(int64_t) * b.N, hipMemcpyHostToDevice, s));
+  MLFF_HIP(ctx, hipMemcpyAsync(b.iperm, b.hperm.data(), sizeof(int64_t) * b.N, hipMemcpyHostToDevice, s));
+  if (!ctx->has_matrix) {
+    MLFF_TRY(operator_diag(ctx, ctx->dwork));
+    MLFF_HIP(ctx, hipMemsetAsync(ctx->xg, 0, sizeof(double) * ctx->ld, s));
   } else {
-  stamp_at(0);
+    launch_diag_of(ctx->K, ctx->ld, b.nrows, ctx->row0, ctx->rows_per, b.blk, ctx->sigma_K, ctx->dwork, s);
+  }
+  MLFF_HIP(ctx, hipMemsetAsync(ctx->pivflag, 0, sizeof(int) * b.blk, s));
+  MLFF_HIP(ctx, hipMemsetAsync(ctx->lr.T, 0, sizeof(double) * round_up(k, 8) * b.blk, s));
+  MLFF_HIP(ctx, hipMemsetAsync(&ctx->st->pivot_err, 0, sizeof(int), s));
+  return MLFF_OK;
+}
+
+// a new speculative block at column m: candidates from the residual diagonal after step m - 1,
+// and the Schur sums of all of them over the columns [0, m) in one GEMM
+static int piv_spec_block(mlff_ctx *ctx, const PivBuild &b, int64_t m) {
+  hipStream_t s = ctx->stream;
+  hipLaunchKernelGGL(k_spec_top_part, dim3(kSpecGroups), dim3(256), 0, s, ctx->dwork,
+                     ctx->pivflag, b.nrows, b.cv, b.ci);
+  hipLaunchKernelGGL(k_spec_top_merge, dim3(kSpecMergeWG), dim3(256), 0, s, (const double *)b.cv,
+                     (const long long *)b.ci, b.Cspec);
+  hipLaunchKernelGGL(k_spec_gather, dim3((unsigned)std::min<int64_t>((m * kSpecC + 255) / 256, 4096)),
+                     dim3(256), 0, s, ctx->lr.T, b.blk, m, b.Cspec, b.Aspec);
+  return gemm_splitk(ctx, true, false, kSpecC, b.blk, m, b.Aspec, kSpecC, ctx->lr.T, b.blk, b.Gspec, b.blk);
+}
+
+// Per-column build times (incomplete_cholesky.py:48-80 records time_cholesky[m] for every
+// column; tools/create_data.py:117-148 compares the first 20 with the rest): device events
+// between segments of columns, owned here and destroyed with the owner, and the persistent
+// form's per-step clocks, which split a launch's time over its steps.
+struct PivStamps {
+  hipStream_t s;
+  std::vector<hipEvent_t> ev;
+  std::vector<int64_t> col;                          // the column each event precedes
+  const unsigned long long *step_clock = nullptr;    // device, 2 k (null: segments split evenly)
+  explicit PivStamps(hipStream_t stream) : s(stream) {}
+  PivStamps(PivStamps &&) = default;  // (a moved-from vector is empty)
+  PivStamps(const PivStamps &) = delete;
+  PivStamps &operator=(const PivStamps &) = delete;
+  ~PivStamps() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+  static constexpr int64_t kEvery = 4;  // the launch sequence stamps every kEvery columns
+  void stamp_at(int64_t m) {
+    hipEvent_t e = nullptr;
+    if (hipEventCreateWithFlags(&e, timing_event_flags()) != hipSuccess) return;
+    hipEventRecord(e, s);
+    ev.push_back(e);
+    col.push_back(m);
+  }
+};
+
+// ctx->piv_col_s from the stamps of a finished build (the stream synchronised): each segment's
+// event time over its columns, evenly or (persistent form) in proportion to the steps' own
+// device clocks
+static int piv_column_times(mlff_ctx *ctx, int64_t k, const PivStamps &st) {
+  ctx->piv_col_s.assign((size_t)k, 0.0);
+  std::vector<unsigned long long> clk;
+  if (st.step_clock != nullptr && k > 0) {
+    clk.resize((size_t)2 * k);
+    MLFF_HIP(ctx, hipMemcpy(clk.data(), st.step_clock, sizeof(unsigned long long) * 2 * k,
+                            hipMemcpyDeviceToHost));
+  }
+  for (size_t g = 0; g + 1 < st.ev.size(); ++g) {
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, st.ev[g], st.ev[g + 1]);
+    const int64_t c0 = st.col[g], c1 = std::min<int64_t>(st.col[g + 1], k);
+    double wsum = 0.0;
+    for (int64_t c = c0; c < c1 && !clk.empty(); ++c)
+      wsum += clk[2 * c + 1] > clk[2 * c] ? (double)(clk[2 * c + 1] - clk[2 * c]) : 0.0;
+    for (int64_t c = c0; c < c1; ++c) {
+      double w = 1.0 / (double)(c1 - c0);
+      if (wsum > 0.0)
+        w = (clk[2 * c + 1] > clk[2 * c] ? (double)(clk[2 * c + 1] - clk[2 * c]) : 0.0) / wsum;
+      ctx->piv_col_s[c] = 1e-3 * ms * w;
+    }
+  }
+  return MLFF_OK;
+}
+
+// MLFF_PIV_TRACE: per step the medians over workgroups of each phase, and the step time
+static int piv_trace_report(mlff_ctx *ctx, int64_t k, int Gp, const unsigned long long *trace) {
+  hipStream_t s = ctx->stream;
+  std::vector<unsigned long long> tr((size_t)k * Gp * 4);
+  MLFF_HIP(ctx, hipMemcpyAsync(tr.data(), trace, sizeof(unsigned long long) * tr.size(),
+                               hipMemcpyDeviceToHost, s));
+  MLFF_HIP(ctx, hipStreamSynchronize(s));
+  double acc[4] = {0, 0, 0, 0};
+  double slow_sum = 0.0, fast_sum = 0.0;  // steps with / without a grid-wide Schur GEMV
+  int64_t cnt = 0, slow = 0;
+  for (int64_t m = 1; m + 1 < k; ++m) {
+    const unsigned long long *a0 = &tr[(size_t)m * Gp * 4], *a1 = &tr[(size_t)(m + 1) * Gp * 4];
+    if (a0[0] == 0 || a1[0] == 0 || a0[3] == 0) continue;  // launch boundaries
+    std::vector<double> ph[4];
+    for (int g = 0; g < Gp; ++g) {
+      const unsigned long long *e = a0 + 4 * g, *f = a1 + 4 * g;
+      ph[0].push_back(10.0 * (double)(e[1] - e[0]));
+      ph[1].push_back(e[2] > e[1] ? 10.0 * (double)(e[2] - e[1]) : 0.0);
+      ph[2].push_back(10.0 * (double)(e[3] - (e[2] > e[1] ? e[2] : e[1])));
+      ph[3].push_back(10.0 * (double)(f[0] - e[0]));
+    }
+    for (int q = 0; q < 4; ++q) {
+      std::nth_element(ph[q].begin(), ph[q].begin() + Gp / 2, ph[q].end());
+      acc[q] += ph[q][Gp / 2];
+    }
+    if (ph[0][Gp / 2] > 20000.0) {
+      ++slow;
+      slow_sum += ph[3][Gp / 2];
+    } else {
+      fast_sum += ph[3][Gp / 2];
+    }
+    ++cnt;
+  }
+  if (cnt > 0)
+    std::fprintf(stderr, "[piv trace] G=%d steps=%lld median ns: winner+stage+miss %.0f, rows %.0f, "
+                 "publish %.0f, step %.0f\n", Gp, (long long)cnt, acc[0] / cnt, acc[1] / cnt,
+                 acc[2] / cnt, acc[3] / cnt);
+  if (cnt > 0)
+    std::fprintf(stderr, "[piv trace] %lld steps > 20 us before the rows (misses): %.2f ms; "
+                 "the other %lld: %.2f ms\n", (long long)slow, 1e-6 * slow_sum,
+                 (long long)(cnt - slow), 1e-6 * fast_sum);
+  return MLFF_OK;
+}
+
+// k_piv_persist's arguments that hold for the whole build; the run sets the granule buffers,
+// the clocks and, per launch, the block, the partials and the step range
+static PersistArgs persist_args(const mlff_ctx *ctx, const PivBuild &b) {
+  PersistArgs pa{};
+  pa.N = b.N;
+  pa.nrows = b.nrows;
+  pa.blk = b.blk;
+  pa.rows_per = ctx->rows_per;
+  pa.Lt = ctx->lr.T;
+  pa.dwork = ctx->dwork;
+  pa.pivflag = ctx->pivflag;
+  pa.perm = ctx->perm;
+  pa.iperm = b.iperm;
+  pa.st = ctx->st;
+  pa.ld = ctx->ld;
+  pa.sigma = ctx->sigma_K;
+  if (ctx->has_matrix) {
+    pa.K = ctx->K;
+  } else {  // the single-column path's data, as mf_columns hands it to k_sgdml_col
+    const MfData &mf = ctx->mf;
+    pa.Rdd = mf.Rdd;
+    pa.M = mf.M;
+    pa.n = mf.n;
+    pa.D = mf.D;
+    pa.i0 = mf.i0;
+    pa.pi = mf.pi_d;
+    pa.piinv = mf.piinv_d;
+    pa.n_perms = mf.n_perms;
+    pa.uvk = mf.uvk;
+    pa.chunks = (3 * mf.n + kColRows - 1) / kColRows;
+  }
+  pa.nrw = (int)b.nrw;
+  pa.part = b.part;
+  pa.kmax_split = b.kmax_split;
+  pa.Cspec = b.Cspec;
+  pa.Gspec = b.Gspec;
+  pa.spec_m0 = -1;
+  pa.mute = -1;
+  return pa;
+}
+
+// the persistent form: one k_piv_persist launch per speculative block (without speculation: one)
+static int piv_run_persist(mlff_ctx *ctx, const PivBuild &b, PivStamps &stamps) {
+  hipStream_t s = ctx->stream;
+  const int64_t k = b.k;
+  const int G = b.Gp;
+  const bool sg = !ctx->has_matrix;
+  // each launch's last partials: G entries, in b.pv / b.pp / pr and pv2 / pp2 / pr2 by turns
+  long long *pr = nullptr, *pp2 = nullptr, *pr2 = nullptr;
+  double *pv2 = nullptr;
+  MLFF_TRY(scratch_alloc(ctx, &pr, G));
+  MLFF_TRY(scratch_alloc(ctx, &pv2, G));
+  MLFF_TRY(scratch_alloc(ctx, &pp2, G));
+  MLFF_TRY(scratch_alloc(ctx, &pr2, G));
+  PersistArgs pa = persist_args(ctx, b);
+  MLFF_TRY(scratch_alloc(ctx, &pa.slots, (size_t)2 * G * kSlot));
+  MLFF_TRY(scratch_alloc(ctx, &pa.flags, (size_t)G));
+  MLFF_TRY(scratch_alloc(ctx, &pa.cands, (size_t)2 * 2 * kSpecC));
+  MLFF_TRY(scratch_alloc(ctx, &pa.step_clock, (size_t)2 * k));
+  double *ccols = nullptr;  // the candidates' columns (sGDML path, speculative blocks)
+  if (sg && b.spec) MLFF_TRY(scratch_alloc(ctx, &ccols, (size_t)kSpecC * b.blk));
+  MLFF_HIP(ctx, hipMemsetAsync(pa.cands, 0, sizeof(unsigned long long) * 2 * 2 * kSpecC, s));
+  MLFF_HIP(ctx, hipMemsetAsync(pa.slots, 0, sizeof(unsigned long long) * 2 * G * kSlot, s));
+  MLFF_HIP(ctx, hipMemsetAsync(pa.flags, 0, sizeof(unsigned long long) * G, s));
+  MLFF_HIP(ctx, hipMemsetAsync(pa.step_clock, 0, sizeof(unsigned long long) * 2 * k, s));
+  stamps.step_clock = pa.step_clock;
+  if (std::getenv("MLFF_PIV_TRACE") != nullptr) {
+    MLFF_TRY(scratch_alloc(ctx, &pa.trace, (size_t)k * G * 4));
+    MLFF_HIP(ctx, hipMemsetAsync(pa.trace, 0, sizeof(unsigned long long) * k * G * 4, s));
+  }
+  if (const char *e = std::getenv("MLFF_PIV_MUTE")) pa.mute = std::atoi(e);
+  const size_t shm = sizeof(double) * (size_t)std::max<int64_t>(k, 8);
+  hipLaunchKernelGGL(k_piv_argmax, dim3(b.np), dim3(256), 0, s, ctx->dwork, ctx->perm, b.N, (int64_t)0,
+                     ctx->row0, b.nrows, b.pv, b.pp);
+  pa.pv_in = b.pv;
+  pa.pp_in = b.pp;
+  pa.pr_in = nullptr;
+  pa.npc = b.np;
+  bool flip = false;
+  stamps.stamp_at(0);
+  for (int64_t m = 0; m < k;) {
+    int64_t m_end = k;
+    pa.spec_m0 = -1;
+    pa.colbuf = nullptr;
+    if (b.spec && m < kSpecMin) {
+      m_end = std::min<int64_t>(k, kSpecMin);
+    } else if (b.spec) {
+      MLFF_TRY(piv_spec_block(ctx, b, m));
+      if (ccols != nullptr)  // the candidates' columns, the steps' hits read them
+        mf_columns(ctx, b.Cspec, kSpecC, ctx->sigma_K, ccols, b.blk);
+      pa.colbuf = ccols;
+      pa.spec_m0 = m;
+      m_end = std::min<int64_t>(k, m + kSpecB);
+    }
+    pa.pv_out = flip ? b.pv : pv2;
+    pa.pp_out = flip ? b.pp : pp2;
+    pa.pr_out = flip ? pr : pr2;
+    pa.m_begin = m;
+    pa.m_end = m_end;
+    if (sg)
+      hipLaunchKernelGGL(k_piv_persist<true>, dim3((unsigned)G), dim3(256), shm, s, pa);
+    else
+      hipLaunchKernelGGL(k_piv_persist<false>, dim3((unsigned)G), dim3(256), shm, s, pa);
+    MLFF_HIP(ctx, hipGetLastError());
+    pa.pv_in = pa.pv_out;
+    pa.pp_in = pa.pp_out;
+    pa.pr_in = pa.pr_out;
+    pa.npc = G;
+    flip = !flip;
+    m = m_end;
+    stamps.stamp_at(m);
+  }
+  hipLaunchKernelGGL(k_perm_from_iperm, dim3((unsigned)std::min<int64_t>((b.N + 255) / 256, 1024)),
+                     dim3(256), 0, s, (const int64_t *)b.iperm, b.N, ctx->perm);
+  if (pa.trace != nullptr) MLFF_TRY(piv_trace_report(ctx, k, G, pa.trace));
+  return MLFF_OK;
+}
+
+// the launch sequence: finaliser, column, split-K Schur GEMV and finisher per step
+static int piv_run_sequence(mlff_ctx *ctx, const PivBuild &b, PivStamps &stamps) {
+  hipStream_t s = ctx->stream;
+  const int64_t k = b.k, N = b.N, nrows = b.nrows, blk = b.blk;
+  const bool multi = ctx->world > 1;
+  double *colbuf = nullptr;  // the pivot's column S e_{m_pi} where there are no dense rows
+  if (!ctx->has_matrix) MLFF_TRY(scratch_alloc(ctx, &colbuf, blk));
+  double *xunit = (b.mfcols && !b.colpath) ? ctx->xg.get() : nullptr;
+  int64_t spec_m0 = -1;  // start of the current speculative block (-1: none)
+  stamps.stamp_at(0);
   for (int64_t m = 0; m < k; ++m) {
-    if (m > 0 && m % kStampEvery == 0) stamp_at(m);
+    if (m > 0 && m % PivStamps::kEvery == 0) stamps.stamp_at(m);
     // candidates of step m: a scan of the positions [m, N) at m = 0 (and on a rank without
     // rows), afterwards the per-workgroup winners k_piv_fin left from step m - 1
-    int npc = (int)gcol;
-    if (m == 0 || gcol == 0) {
-      hipLaunchKernelGGL(k_piv_argmax, dim3(np), dim3(256), 0, s, ctx->dwork, ctx->perm, N, m,
-                         ctx->row0, nrows, pv, pp);
-      npc = np;
+    int npc = (int)b.gcol;
+    if (m == 0 || b.gcol == 0) {
+      hipLaunchKernelGGL(k_piv_argmax, dim3(b.np), dim3(256), 0, s, ctx->dwork, ctx->perm, N, m,
+                         ctx->row0, nrows, b.pv, b.pp);
+      npc = b.np;
     }
-    if (spec && m >= kSpecMin && m % kSpecB == 0) {
-      // a new block: candidates from the residual diagonal after step m - 1, and the
-      // Schur sums of all of them over the columns [0, m) in one GEMM
+    if (b.spec && m >= kSpecMin && m % kSpecB == 0) {
       spec_m0 = m;
-      hipLaunchKernelGGL(k_spec_top_part, dim3(kSpecGroups), dim3(256), 0, s, ctx->dwork,
-                         ctx->pivflag, nrows, cv, ci);
-      hipLaunchKernelGGL(k_spec_top_merge, dim3(kSpecMergeWG), dim3(256), 0, s, (const double *)cv,
-                         (const long long *)ci, Cspec);
-      hipLaunchKernelGGL(k_spec_gather, dim3((unsigned)std::min<int64_t>((m * kSpecC + 255) / 256, 4096)),
-                         dim3(256), 0, s, ctx->lr.T, blk, m, Cspec, Aspec);
-      MLFF_TRY(gemm_splitk(ctx, true, false, kSpecC, blk, m, Aspec, kSpecC, ctx->lr.T, blk, Gspec, blk));
+      MLFF_TRY(piv_spec_block(ctx, b, m));
     }
-    const bool multi = ctx->world > 1;
     if (multi) {
-      double *my = wins + 2 * ctx->rank;
-      hipLaunchKernelGGL(k_piv_rank_winner, dim3(1), dim3(256), 0, s, pv, pp, npc, my);
-      MLFF_TRY(comm_allgather(ctx, my, wins, 2));
+      double *my = b.wins + 2 * ctx->rank;
+      hipLaunchKernelGGL(k_piv_rank_winner, dim3(1), dim3(256), 0, s, b.pv, b.pp, npc, my);
+      MLFF_TRY(comm_allgather(ctx, my, b.wins, 2));
     }
-    double *xunit = (mfcols && !colpath) ? ctx->xg : nullptr;
-    hipLaunchKernelGGL(k_piv_finalize, dim3(1), dim3(256), 0, s, wins, ctx->world,
-                       multi ? nullptr : (const double *)pv,
-                       multi ? nullptr : (const long long *)pp, npc, ctx->perm, m, ctx->row0,
+    hipLaunchKernelGGL(k_piv_finalize, dim3(1), dim3(256), 0, s, b.wins, ctx->world,
+                       multi ? nullptr : (const double *)b.pv,
+                       multi ? nullptr : (const long long *)b.pp, npc, ctx->perm, m, ctx->row0,
                        nrows, ctx->lr.T, blk, ctx->pivflag, multi ? ctx->prow : nullptr, xunit,
-                       ctx->rows_per, blk, ctx->st, iperm, spec_m0 >= 0 ? Cspec : nullptr, hit);
+                       ctx->rows_per, blk, ctx->st, b.iperm, spec_m0 >= 0 ? b.Cspec : nullptr, b.hit);
     if (multi && m > 0) MLFF_TRY(comm_allreduce(ctx, ctx->prow, (size_t)m));
-    if (rbfcols)
+    if (b.rbfcols)
       launch_rbf_cols(ctx->rbf, N, ctx->row0, nrows, nullptr, 1, ctx->st, ctx->sigma_K, colbuf, blk, s);
-    else if (colpath)
+    else if (b.colpath)
       mf_columns(ctx, nullptr, 1, ctx->sigma_K, colbuf, blk);  // column st->m_pi
-    else if (mfcols)
+    else if (b.mfcols)
       launch_mf_operator(ctx, ctx->xg, colbuf, nullptr, nullptr, ctx->sigma_K, 0.0);
-    const int ks = m > 0 ? std::min(kmax_split, choose_ksplit(m, blk)) : 0;
+    const int ks = m > 0 ? std::min(b.kmax_split, choose_ksplit(m, blk)) : 0;
     const bool in_spec = spec_m0 >= 0;
     // Schur column GEMV over L[:, :m] (on a speculation hit only over [spec_m0, m)); the
     // panel's leading rows (up to 128 MB) are read with default-policy loads so they stay in
     // the MALL from one step to the next
     if (ks > 0)
-      launch_colgemv_part(ctx->lr.T, blk, m, ctx->prow, 1, m, ks, part, nullptr, s, StopFold{},
+      launch_colgemv_part(ctx->lr.T, blk, m, ctx->prow, 1, m, ks, b.part, nullptr, s, StopFold{},
                           panel_cached_rows(m, blk),
                           multi ? nullptr : (const long long *)&ctx->st->m_pi,
-                          in_spec ? hit : nullptr, in_spec ? spec_m0 : 0);
-    if (gcol > 0)
-      hipLaunchKernelGGL(k_piv_fin, dim3(gcol), dim3(256), 0, s, ctx->K, ctx->ld, ctx->sigma_K,
-                       (const double *)colbuf, ctx->rows_per, blk, nrows, m, part, ks, blk,
-                       ctx->lr.T, blk, ctx->pivflag, ctx->dwork, ctx->st, xunit, iperm, ctx->row0, N,
-                       pv, pp, (const double *)Gspec, in_spec ? (const int *)hit : nullptr);
-    else if (mfcols && !colpath)
+                          in_spec ? b.hit : nullptr, in_spec ? spec_m0 : 0);
+    if (b.gcol > 0)
+      hipLaunchKernelGGL(k_piv_fin, dim3(b.gcol), dim3(256), 0, s, ctx->K, ctx->ld, ctx->sigma_K,
+                         (const double *)colbuf, ctx->rows_per, blk, nrows, m, b.part, ks, blk,
+                         ctx->lr.T, blk, ctx->pivflag, ctx->dwork, ctx->st, xunit, b.iperm, ctx->row0, N,
+                         b.pv, b.pp, (const double *)b.Gspec, in_spec ? (const int *)b.hit : nullptr);
+    else if (b.mfcols && !b.colpath)
       hipLaunchKernelGGL(k_unit_pivot, dim3(1), dim3(64), 0, s, ctx->xg, ctx->rows_per, blk,
                          ctx->st, 0.0);
     if ((m & 255) == 255) MLFF_HIP(ctx, hipGetLastError());
   }
-  stamp_at(k);
-  }
-  MLFF_HIP(ctx, hipGetLastError());
-  int perr = 0;
-  MLFF_HIP(ctx, hipMemcpyAsync(&perr, &ctx->st->pivot_err, sizeof(int), hipMemcpyDeviceToHost, s));
-  if (index_columns_out != nullptr)
-    MLFF_HIP(ctx, hipMemcpyAsync(index_columns_out, ctx->perm, sizeof(int64_t) * N,
-                                 hipMemcpyDeviceToHost, s));
-  MLFF_HIP(ctx, hipStreamSynchronize(s));
-  ctx->piv_col_s.assign((size_t)k, 0.0);
-  std::vector<unsigned long long> clk;
-  if (step_clock != nullptr && k > 0) {
-    clk.resize((size_t)2 * k);
-    MLFF_HIP(ctx, hipMemcpy(clk.data(), step_clock, sizeof(unsigned long long) * 2 * k,
-                            hipMemcpyDeviceToHost));
-  }
-  if (stamp_col.size() == stamps.size()) {
-    // each segment's event time over its columns: evenly, or (persistent form) in proportion to
-    // the steps' own device clocks
-    for (size_t g = 0; g + 1 < stamps.size(); ++g) {
-      float ms = 0.f;
-      (void)hipEventElapsedTime(&ms, stamps[g], stamps[g + 1]);
-      const int64_t c0 = stamp_col[g], c1 = std::min<int64_t>(stamp_col[g + 1], k);
-      double wsum = 0.0;
-      for (int64_t c = c0; c < c1 && !clk.empty(); ++c)
-        wsum += clk[2 * c + 1] > clk[2 * c] ? (double)(clk[2 * c + 1] - clk[2 * c]) : 0.0;
-      for (int64_t c = c0; c < c1; ++c) {
-        double w = 1.0 / (double)(c1 - c0);
-        if (wsum > 0.0)
-          w = (clk[2 * c + 1] > clk[2 * c] ? (double)(clk[2 * c + 1] - clk[2 * c]) : 0.0) / wsum;
-        ctx->piv_col_s[c] = 1e-3 * ms * w;
-      }
-    }
-  }
-  for (hipEvent_t e : stamps) (void)hipEventDestroy(e);
-  if (perr == 2 && persist) {
-    // a workgroup of the persistent grid waited > 1 s for the others (not co-resident: another
-    // process's kernels hold CUs): this context builds with the launch sequence from now on
-    ctx->piv_persist_off = true;
-    return pivoted_cholesky(ctx, k, index_columns_out);
-  }
-  if (perr)
-    return set_error(ctx, MLFF_ERR_NOT_PSD,
-                     "given matrix is not PSD (pivot <= 0 in pivoted Cholesky)");
+  stamps.stamp_at(k);
   return MLFF_OK;
 }
 
+int pivoted_cholesky(mlff_ctx *ctx, int64_t k, int64_t *index_columns_out) {
+  hipStream_t s = ctx->stream;
+  for (;;) {  // at most twice: the persistent form, and after its timeout the launch sequence
+    ScratchScope scope(ctx);
+    PivStamps stamps(s);
+    PivBuild b;
+    MLFF_TRY(piv_setup(ctx, k, &b));
+    const bool persist = b.Gp > 0;
+    MLFF_TRY(persist ? piv_run_persist(ctx, b, stamps) : piv_run_sequence(ctx, b, stamps));
+    MLFF_HIP(ctx, hipGetLastError());
+    int perr = 0;
+    MLFF_HIP(ctx, hipMemcpyAsync(&perr, &ctx->st->pivot_err, sizeof(int), hipMemcpyDeviceToHost, s));
+    if (index_columns_out != nullptr)
+      MLFF_HIP(ctx, hipMemcpyAsync(index_columns_out, ctx->perm, sizeof(int64_t) * b.N,
+                                   hipMemcpyDeviceToHost, s));
+    MLFF_HIP(ctx, hipStreamSynchronize(s));
+    MLFF_TRY(piv_column_times(ctx, k, stamps));
+    if (perr == 2 && persist) {
+      // a workgroup of the persistent grid waited > 1 s for the others (not co-resident: another
+      // process's kernels hold CUs): this context builds with the launch sequence from now on;
+      // this attempt's scratch and stamps are released before the next begins
+      ctx->piv_persist_off = true;
+      continue;
+    }
+    if (perr)
+      return set_error(ctx, MLFF_ERR_NOT_PSD,
+                       "given matrix is not PSD (pivot <= 0 in pivoted Cholesky)");
+    return MLFF_OK;
+  }
+}
+
 }  // namespace mlff
+

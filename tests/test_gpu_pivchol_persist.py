@@ -95,6 +95,42 @@ def test_persistent_matches_launch_sequence_dense(sg, monkeypatch, n, k):
     np.testing.assert_allclose(a[1][:kk].T[:n], L_ref, rtol=0, atol=1e-10)
 
 
+@pytest.fixture(scope="module")
+def dense513():
+    n = 513  # the smallest size with speculation: nrows > kSpecGroups * kSpecPer = 512
+    X = np.random.default_rng(3).uniform(size=(n, 3))
+    d2 = ((X[:, None, :] - X[None, :, :]) ** 2).sum(-1)
+    K = np.exp(-d2 / (2 * 0.3 ** 2)) + 1e-6 * np.eye(n)
+    K.setflags(write=False)
+    return K
+
+
+@pytest.mark.parametrize("k", [80, 81, 96, 97])
+def test_block_loop_edges_dense(sg, monkeypatch, dense513, k):
+    """The block loop both forms share (piv_spec_block and its callers), at the panel sizes where
+    the blocks' ends move: speculation needs k > kSpecMin + kSpecB = 80, so k = 80 has no block;
+    81 one full block [64, 80) and a one-step block; 96 blocks that end exactly at k; 97 a
+    one-step tail again.  The two forms agree bit for bit and both report every column's time."""
+    K = dense513
+    n = K.shape[0]
+
+    def setup(s):
+        s.set_matrix(K)
+        s.set_operator(1.0, 1e-6)
+
+    a = _build(sg, monkeypatch, True, setup, n, k)
+    b = _build(sg, monkeypatch, False, setup, n, k)
+    _compare(a, b, k)
+    assert a[4].shape == (k,) and np.all(a[4] > 0)
+    assert b[4].shape == (k,) and np.all(b[4] > 0)
+    from oracle.precon import pivoted_cholesky
+
+    kk = 10  # (random points: later candidates can tie to rounding)
+    L_ref, piv_ref = pivoted_cholesky(lambda i: K[:, i].copy(), np.diag(K).copy(), kk)
+    np.testing.assert_array_equal(a[0][:kk], piv_ref[:kk])
+    np.testing.assert_allclose(a[1][:kk].T[:n], L_ref, rtol=0, atol=1e-10)
+
+
 @pytest.mark.timeout(600)
 def test_persistent_configs1_full_size(sg, monkeypatch):
     """configs[1]: N = 15540, the rule-of-thumb k = 2701 -- the factor bit-identical to the launch
