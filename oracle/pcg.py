@@ -23,15 +23,32 @@ import numpy as np
 
 
 def cg_legacy(matvec, b, x0=None, tol=1e-5, maxiter=None, psolve=None, callback=None,
-              dot_fn=None):
-    """Returns (x, info, trace, iters).  trace[0] = ||r0||, trace[j] = stop-test ||r_j||."""
-    b = np.asarray(b, dtype=np.float64)
+              dot_fn=None, dtype=np.float64, record=None):
+    """Returns (x, info, trace, iters).  trace[0] = ||r0||, trace[j] = stop-test ||r_j||.
+
+    dtype: np.float64 (the default: scipy's own arithmetic, bit for bit) or np.longdouble, where
+    b, x, tol, the sums and the norms stay in long double; matvec and psolve are the caller's and
+    must return that dtype.  record: a dict that receives "x" = [x_0, ..., x_iters] (copies) and
+    "recheck" = [(it, recurrence resid, true resid, passed)], one entry per true-residual test."""
+    f64 = np.dtype(dtype) == np.float64
+    b = np.asarray(b, dtype=dtype)
     n = b.size
     maxiter = 10 * n if maxiter is None else int(maxiter)
-    dot = dot_fn if dot_fn is not None else (lambda u, v: float(np.dot(u, v)))
-    norm = lambda u: float(np.sqrt(dot(u, u)))
+    if dot_fn is not None:
+        dot = dot_fn
+    elif f64:
+        dot = lambda u, v: float(np.dot(u, v))
+    else:
+        dot = lambda u, v: dtype(np.dot(u, v))
+    norm = (lambda u: float(np.sqrt(dot(u, u)))) if f64 else (lambda u: np.sqrt(dot(u, u)))
+    if not f64:
+        tol = dtype(tol)
     psolve = psolve if psolve is not None else (lambda v: v)
-    x = np.zeros(n) if x0 is None else np.array(x0, dtype=np.float64)
+    x = np.zeros(n, dtype=dtype) if x0 is None else np.array(x0, dtype=dtype)
+    xs = rechecks = None
+    if record is not None:
+        xs, rechecks = record.setdefault("x", []), record.setdefault("recheck", [])
+        xs.append(x.copy())
     bnrm2 = norm(b)
     # _get_atol legacy
     resid0 = norm(matvec(x) - b)
@@ -69,10 +86,15 @@ def cg_legacy(matvec, b, x0=None, tol=1e-5, maxiter=None, psolve=None, callback=
         resid = norm(r)
         conv = resid <= atol
         if conv and it > 1:
+            recurrence = resid
             r = b - matvec(x)
             resid = norm(r)
             conv = resid <= atol
+            if rechecks is not None:
+                rechecks.append((it, recurrence, resid, bool(conv)))
         trace.append(resid)
+        if xs is not None:
+            xs.append(x.copy())
         if conv:
             info = 0
             break
