@@ -435,20 +435,24 @@ inline unsigned timing_event_flags() {
   return f;
 }
 
+// What a timed segment of a PCG iteration brackets (pcg.hip mark_begin / mark_end): the operator,
+// the low-rank preconditioner apply, a collective of the sharded iteration (one rank's stream),
+// or the T r half that the ranks iteration issues ahead of the next apply -- its time goes to
+// that apply, which is counted once, by its z half (kSegPrecon).  The first three index Timing::seg.
+enum SegKind : int { kSegOperator = 0, kSegPrecon = 1, kSegComm = 2, kSegPreconTail = 3 };
+
 struct Timing {
   bool on = false;
   int every = 1;        // bracket every `every`-th PCG iteration only (mlff_timing_enable)
   bool sample = true;   // the iteration being launched is bracketed
   std::vector<hipEvent_t> ev;  // pool, pairs (start, stop)
   size_t used = 0;             // events used in the current chunk
-  double gemv_ms = 0.0;
-  int64_t gemv_count = 0;
-  double pre_ms = 0.0;     // low-rank preconditioner apply (one rank)
-  int64_t pre_count = 0;
-  double iter_ms = 0.0;
-  int64_t iter_count = 0;
-  double comm_ms = 0.0;    // collectives of the sharded iteration (one rank's stream)
-  int64_t comm_count = 0;
+  struct Bucket {
+    double ms = 0.0;
+    int64_t count = 0;
+  };
+  Bucket seg[3];  // by SegKind: operator, preconditioner apply, collectives
+  Bucket iter;    // whole chunks and the iterations completed in them
   Timing() = default;
   Timing(const Timing &) = delete;
   Timing &operator=(const Timing &) = delete;
@@ -1085,11 +1089,29 @@ int pred_fd_slab(mlff_ctx *ctx, const double *R, int64_t nq, bool with_fd);
 int pred_hess_run(mlff_ctx *ctx, const double *R, int64_t Q, double *H_out);
 void pred_hess_work(const PredData &pd, double *flops_per_query, double *bytes_per_query);
 
-// ---- operator access for the builds (api.hip) --------------------------------
+// ---- operator access for the builds and the PCG driver (api.hip) --------------
 // require the operator and resolve its storage (builds the tiles if they are to be used)
 int operator_prepare(mlff_ctx *ctx);
 // y_loc = sigma_K K x over this rank's rows; x_loc = this rank's block (blk entries)
 int operator_apply_local(mlff_ctx *ctx, const double *x_loc, double *y_loc);
+// operator_prepare's two steps, for the PCG driver (pcg.hip)
+int require_operator(mlff_ctx *ctx);
+int resolve_storage(mlff_ctx *ctx);
+// y_loc = sigma_K K v_full + lam v_loc over this rank's rows (status gated); pq_part: also the
+// v_loc . y_loc partials of the CG step; pf: the fused search-direction update
+int launch_operator(mlff_ctx *ctx, const double *v_full, double *y_loc, const double *v_loc,
+                    const int *status, double *pq_part = nullptr, const PFuse *pf = nullptr);
+// gather the rank blocks of an ld-long padded vector (in place)
+int allgather_blocks(mlff_ctx *ctx, double *full);
+
+// ---- low-rank preconditioner apply (pcg.hip) ----------------------------------
+// the halves of the two-pass apply, and the apply in the form the build chose
+int lowrank_tr(mlff_ctx *ctx, const double *r, const int *status, StopFold fold = StopFold{},
+               bool reduce = true);
+void lowrank_z(mlff_ctx *ctx, const double *r, double *z, double *rho, const int *status,
+               StopFold fold = StopFold{});
+int lowrank_apply(mlff_ctx *ctx, const double *r, double *z, double *rho, const int *status,
+                  int *fault, StopFold fold = StopFold{}, XrFold xf = XrFold{});
 
 // ---- eigen preconditioner (kernels_eig.hip) ----------------------------------
 int eig_lowrank(mlff_ctx *ctx, int64_t k, int mask_mode, int64_t dim_i, double *Lt_out,

@@ -1,6 +1,6 @@
 """World-size-2 checks of the row-sharded PCG protocol on CPU (gloo).
 
-The GPU library runs this exact protocol with RCCL (api.hip launch_iteration_ranks):
+The GPU library runs this exact protocol with RCCL (pcg.hip launch_iteration_ranks):
 every rank owns a contiguous, padded row block; dots are fixed-length partial-sum
 arrays; per iteration there are three collectives:
   1. allgather(z_g | rho partials of r_g.z_g) -> every rank sums all ranks' partials
