@@ -245,6 +245,11 @@ int mlff_sgdml_descriptors(const double *R, int64_t M, int n_atoms, double *R_de
  * the device library's exp (the stored tiles, rows and columns) into lib_out and by the
  * select-free form of the tile mat-vec's generating role into lean_out.  Test hook. */
 int mlff_test_rbf_exp(mlff_ctx *ctx, const double *s, int64_t n, double *lib_out, double *lean_out);
+/* The same with the generating role's form for operators whose points keep every squared
+ * distance small (mlff_sym_gen_info): no clamp of s.  Every s must lie in [0, 2150], else
+ * MLFF_ERR_ARG.  Test hook. */
+int mlff_test_rbf_exp_noclamp(mlff_ctx *ctx, const double *s, int64_t n, double *lib_out,
+                              double *lean_out);
 
 /* operator A = sigma_K * K + lam * I.  sGDML: sigma_K = -1 (K is negative
  * semidefinite, the solved system is (-K + lam I) x = y, iterative_solver.py:995);
@@ -332,6 +337,14 @@ int mlff_storage_info(mlff_ctx *ctx, int *mode_out, double *bytes_per_matvec_out
  * constant -- where the rank has at least two work units per workgroup (MLFF_SYM_WGS=3:
  * always; =2: never); every other tile operator runs two. */
 int mlff_sym_launch_info(mlff_ctx *ctx, int *wgs_per_cu_out, int64_t *grid_out);
+/* The generating role's entry form of a tile operator generated from RBF points (else
+ * MLFF_ERR_STATE).  extent2_out: the squared diagonal of the bounding box of the points divided
+ * by the length scale, which no squared distance exceeds.  noclamp_out: 1 where every point is
+ * finite and extent2 <= 2048, so that exp(-0.5 s) of an unpadded off-diagonal tile is evaluated
+ * without the clamp of s that keeps the exponent's scaling in range; 0 otherwise, with
+ * MLFF_SYM_GEN_CLAMP=1 at the operator's build, and where no workgroup generates.  The result's
+ * bits do not depend on it. */
+int mlff_sym_gen_info(mlff_ctx *ctx, int *noclamp_out, double *extent2_out);
 /* form of the matrix-free sGDML operator (MLFF_STORAGE_MATFREE; the reference's K_op,
  * iterative_solver.py:383-445 / predict.py:172-220, evaluated three ways):
  * MLFF_MF_FORM_PAIR (pair sums, then F, then J^T), MLFF_MF_FORM_REC (record-factored: x-independent

@@ -1131,6 +1131,20 @@ int mlff_gen_rbf(mlff_ctx *ctx, const double *X, int d, double length_scale, dou
   // diagonal and (for the DENSE storage only) the rows are evaluated from them on device
   std::vector<double> Xs((size_t)ctx->N * d);
   for (size_t i = 0; i < Xs.size(); ++i) Xs[i] = X[i] / length_scale;
+  // the squared diagonal of the scaled points' box bounds every squared distance: where it is
+  // small enough the tile mat-vec's generating role drops its clamp (SymGen::noclamp)
+  bool finite = true;
+  double extent2 = 0.0;
+  for (int t = 0; t < d; ++t) {
+    double lo = INFINITY, hi = -INFINITY;
+    for (int64_t i = 0; i < ctx->N; ++i) {
+      const double x = Xs[(size_t)i * d + t];
+      finite = finite && std::isfinite(x);
+      lo = std::min(lo, x);
+      hi = std::max(hi, x);
+    }
+    extent2 += (hi - lo) * (hi - lo);
+  }
   ctx->sym = SymPack{};
   ctx->mf = MfData();
   rbf_free(ctx);
@@ -1140,6 +1154,8 @@ int mlff_gen_rbf(mlff_ctx *ctx, const double *X, int d, double length_scale, dou
   MLFF_HIP(ctx, hipMemcpy(ctx->rbf.Xs, Xs.data(), sizeof(double) * Xs.size(), hipMemcpyHostToDevice));
   ctx->rbf.d = d;
   ctx->rbf.jitter = jitter;
+  ctx->rbf.extent2 = extent2;
+  ctx->rbf.finite = finite;
   ctx->rbf.ready = true;
   ctx->K_symmetric = true;
   return MLFF_OK;
@@ -1287,23 +1303,41 @@ int mlff_set_energy_constraints(mlff_ctx *ctx, int use_E_cstr) {
   MLFF_API_END(ctx)
 }
 
-int mlff_test_rbf_exp(mlff_ctx *ctx, const double *s, int64_t n, double *lib_out, double *lean_out) {
-  MLFF_API_BEGIN
-  MLFF_ENTER(ctx);
+// both probe hooks: the library's exp and the generating role's, with or without its clamp
+static int test_rbf_exp(mlff_ctx *ctx, const double *s, int64_t n, double *lib_out, double *lean_out,
+                        bool clamp) {
   if (s == nullptr || lib_out == nullptr || lean_out == nullptr || n < 1)
     return set_error(ctx, MLFF_ERR_ARG, "test_rbf_exp: bad arguments");
+  if (!clamp)
+    for (int64_t i = 0; i < n; ++i)
+      if (!(s[i] >= 0.0 && s[i] <= 2150.0))
+        return set_error(ctx, MLFF_ERR_ARG, "test_rbf_exp_noclamp: need 0 <= s <= 2150");
   ScratchScope scope(ctx);
   double *ds = nullptr, *da = nullptr, *db = nullptr;
   MLFF_TRY(scratch_alloc(ctx, &ds, (size_t)n));
   MLFF_TRY(scratch_alloc(ctx, &da, (size_t)n));
   MLFF_TRY(scratch_alloc(ctx, &db, (size_t)n));
   MLFF_HIP(ctx, hipMemcpyAsync(ds, s, sizeof(double) * n, hipMemcpyHostToDevice, ctx->stream));
-  launch_rbf_exp_probe(ds, n, da, db, ctx->stream);
+  launch_rbf_exp_probe(ds, n, da, db, clamp, ctx->stream);
   MLFF_HIP(ctx, hipGetLastError());
   MLFF_HIP(ctx, hipMemcpyAsync(lib_out, da, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
   MLFF_HIP(ctx, hipMemcpyAsync(lean_out, db, sizeof(double) * n, hipMemcpyDeviceToHost, ctx->stream));
   MLFF_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return MLFF_OK;
+}
+
+int mlff_test_rbf_exp(mlff_ctx *ctx, const double *s, int64_t n, double *lib_out, double *lean_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  return test_rbf_exp(ctx, s, n, lib_out, lean_out, true);
+  MLFF_API_END(ctx)
+}
+
+int mlff_test_rbf_exp_noclamp(mlff_ctx *ctx, const double *s, int64_t n, double *lib_out,
+                              double *lean_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  return test_rbf_exp(ctx, s, n, lib_out, lean_out, false);
   MLFF_API_END(ctx)
 }
 
@@ -1476,6 +1510,19 @@ int mlff_sym_launch_info(mlff_ctx *ctx, int *wgs_per_cu_out, int64_t *grid_out) 
   if (!ctx->use_sym || !ctx->sym.ready) return set_error(ctx, MLFF_ERR_STATE, "no symmetric tile operator");
   if (wgs_per_cu_out) *wgs_per_cu_out = ctx->sym.wgs;
   if (grid_out) *grid_out = ctx->sym.dyn;
+  return MLFF_OK;
+  MLFF_API_END(ctx)
+}
+
+int mlff_sym_gen_info(mlff_ctx *ctx, int *noclamp_out, double *extent2_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  MLFF_TRY(require_operator(ctx));
+  MLFF_TRY(resolve_storage(ctx));
+  if (!ctx->use_sym || !ctx->sym.ready) return set_error(ctx, MLFF_ERR_STATE, "no symmetric tile operator");
+  if (!ctx->rbf.ready) return set_error(ctx, MLFF_ERR_STATE, "the tiles were not generated from RBF points");
+  if (noclamp_out) *noclamp_out = ctx->sym.gen ? ctx->sym.gsrc.noclamp : 0;
+  if (extent2_out) *extent2_out = ctx->rbf.extent2;
   return MLFF_OK;
   MLFF_API_END(ctx)
 }

@@ -143,7 +143,14 @@ struct SymGen {
   int pool_first = 0;  // a role done with its own range: 0 the other role's range, then the
                        // quarter units; 1 the quarter units first (MLFF_SYM_STEAL=pool)
   int wgs = 2;    // resident workgroups per CU: one of them streams, the others generate
+  int noclamp = 0;  // plain tiles evaluate their entries without the clamp of the squared
+                    // distance: every point finite and RbfData::extent2 <= kSymGenNoClampExtent2
+                    // (decided at the operator's build; MLFF_SYM_GEN_CLAMP=1: never)
 };
+// Largest squared diagonal of the scaled points' bounding box for which no squared distance can
+// reach the 2150 that rbf_of_sqdist_lean<false> is good for: 5 % below it, the fma chain that
+// forms a squared distance being 1e-15 relative
+constexpr double kSymGenNoClampExtent2 = 2048.0;
 // A workgroup's role: by its arrival count on its CU (of every SymGen::wgs arrivals the first
 // streams, the others generate: one streaming workgroup on every CU whatever the dispatcher's
 // placement), by blockIdx.x in the same way (the first rule, A/B), or every workgroup in one
@@ -352,6 +359,10 @@ struct RbfData {
   DevBuf<double> Xs;  // N x d
   int d = 0;
   double jitter = 0.0;
+  // sum over the dimensions of (max - min)^2 of the scaled points: no squared distance between
+  // two of them is larger.  finite: every coordinate is (else extent2 means nothing)
+  double extent2 = 0.0;
+  bool finite = false;
 };
 
 // K[i, g] (i != g) of the sklearn RBF kernel: exp(-0.5 * sum_t (xs_i - xs_g)^2).  The squared
@@ -377,21 +388,37 @@ __device__ __forceinline__ double rbf_of_sqdist(double s) { return exp(-0.5 * s)
 __device__ __forceinline__ double rbf_exp_c(unsigned long long bits) {
   return __builtin_bit_cast(double, bits);
 }
+//
+// The sequence runs on s itself, without the multiply by -0.5.  Scaling by a power of two
+// commutes with IEEE rounding (no intermediate or constant comes near the denormal range: the
+// smallest coefficient is about 2.5e-8 * 2^-11), so with x = -0.5 s, R = -2 r and P_k =
+// (-1/2)^k p_k the library's steps n = rint(x log2e), r = fma(-n, ln2_hi, x), r = fma(-n,
+// ln2_lo, r), p_k = fma(r, p_{k+1}, c_k) become n = rint(s (-log2e / 2)), R = fma(n, 2 ln2_hi,
+// s), R = fma(n, 2 ln2_lo, R), P_k = fma(R, P_{k+1}, (-1/2)^k c_k): every constant is the
+// library's times an exact power of two (written beside it below), every intermediate the
+// library's times an exact power of two, n and P_0 = p_0 the library's own.  The one place
+// where the library's form rounds and this one does not is -0.5 s of a denormal s; n = 0 and
+// the result 1.0 either way.  The clamp at x = -1075 is min(s, 2150) here.
+// CLAMP false leaves it out: domain 0 <= s <= 2150, for the plain tiles of an operator whose
+// point set is known to stay inside it (SymGen::noclamp); the same bits there.
+template <bool CLAMP = true>
 __device__ __forceinline__ double rbf_of_sqdist_lean(double s) {
-  const double x = __builtin_fmax(-0.5 * s, -1075.0);
-  const double n = __builtin_rint(__dmul_rn(x, rbf_exp_c(0x3FF71547652B82FEull)));
-  double r = fma(-n, rbf_exp_c(0x3FE62E42FEFA39EFull), x);
-  r = fma(-n, rbf_exp_c(0x3C7ABC9E3B39803Full), r);
-  double p = fma(r, rbf_exp_c(0x3E5ADE156A5DCB37ull), rbf_exp_c(0x3E928AF3FCA7AB0Cull));
-  p = fma(r, p, rbf_exp_c(0x3EC71DEE623FDE64ull));
-  p = fma(r, p, rbf_exp_c(0x3EFA01997C89E6B0ull));
-  p = fma(r, p, rbf_exp_c(0x3F2A01A014761F6Eull));
-  p = fma(r, p, rbf_exp_c(0x3F56C16C1852B7B0ull));
-  p = fma(r, p, rbf_exp_c(0x3F81111111122322ull));
-  p = fma(r, p, rbf_exp_c(0x3FA55555555502A1ull));
-  p = fma(r, p, rbf_exp_c(0x3FC5555555555511ull));
-  p = fma(r, p, rbf_exp_c(0x3FE000000000000Bull));
-  p = fma(r, p, 1.0);
+  if constexpr (CLAMP) s = __builtin_fmin(s, 2150.0);
+  // -log2e / 2 (log2e 0x3FF71547652B82FE)
+  const double n = __builtin_rint(__dmul_rn(s, rbf_exp_c(0xBFE71547652B82FEull)));
+  double r = fma(n, rbf_exp_c(0x3FF62E42FEFA39EFull), s);  // 2 ln2_hi (0x3FE62E42FEFA39EF)
+  r = fma(n, rbf_exp_c(0x3C8ABC9E3B39803Full), r);         // 2 ln2_lo (0x3C7ABC9E3B39803F)
+  // (-1/2)^11 c_11 (0x3E5ADE156A5DCB37), (-1/2)^10 c_10 (0x3E928AF3FCA7AB0C)
+  double p = fma(r, rbf_exp_c(0xBDAADE156A5DCB37ull), rbf_exp_c(0x3DF28AF3FCA7AB0Cull));
+  p = fma(r, p, rbf_exp_c(0xBE371DEE623FDE64ull));  // -2^-9 c_9 (0x3EC71DEE623FDE64)
+  p = fma(r, p, rbf_exp_c(0x3E7A01997C89E6B0ull));  // 2^-8 c_8 (0x3EFA01997C89E6B0)
+  p = fma(r, p, rbf_exp_c(0xBEBA01A014761F6Eull));  // -2^-7 c_7 (0x3F2A01A014761F6E)
+  p = fma(r, p, rbf_exp_c(0x3EF6C16C1852B7B0ull));  // 2^-6 c_6 (0x3F56C16C1852B7B0)
+  p = fma(r, p, rbf_exp_c(0xBF31111111122322ull));  // -2^-5 c_5 (0x3F81111111122322)
+  p = fma(r, p, rbf_exp_c(0x3F655555555502A1ull));  // 2^-4 c_4 (0x3FA55555555502A1)
+  p = fma(r, p, rbf_exp_c(0xBF95555555555511ull));  // -2^-3 c_3 (0x3FC5555555555511)
+  p = fma(r, p, rbf_exp_c(0x3FC000000000000Bull));  // 2^-2 c_2 (0x3FE000000000000B)
+  p = fma(r, p, -0.5);                              // -2^-1 c_1 (1.0)
   p = fma(r, p, 1.0);
   return __builtin_ldexp(p, (int)n);
 }
@@ -986,8 +1013,9 @@ struct PGather {
   DevState *st = nullptr;
   long long it = 0;
 };
-// test hook: lib_out[i] = rbf_of_sqdist(s[i]), lean_out[i] = rbf_of_sqdist_lean(s[i]) (device arrays)
-void launch_rbf_exp_probe(const double *s, int64_t n, double *lib_out, double *lean_out,
+// test hook: lib_out[i] = rbf_of_sqdist(s[i]), lean_out[i] = rbf_of_sqdist_lean<clamp>(s[i])
+// (device arrays; !clamp: every s[i] in [0, 2150])
+void launch_rbf_exp_probe(const double *s, int64_t n, double *lib_out, double *lean_out, bool clamp,
                           hipStream_t st);
 // P <- slot partials of K v_full over the stored tiles
 void launch_symv(const SymPack &sp, const double *v_full, double *P, const int *status,

@@ -233,12 +233,16 @@ __device__ __forceinline__ bool gen_block_full(const SymGen &gs, int Jb) {
 }
 // row r (tile-local) of a generated tile: the 8 entries of the lane's columns, the bits
 // k_sym_gen_rbf stores (rbf_of_sqdist_lean: exp's bits, common.h).  PLAIN: an off-diagonal tile
-// without padding, which nearly every tile is -- no select and no compare in the row
-template <bool PLAIN, bool DIAG>
+// without padding, which nearly every tile is -- no select and no compare in the row.  CLAMP:
+// the entry's form (rbf_of_sqdist_lean); false only in plain tiles of an operator whose points
+// keep every squared distance in that form's domain (SymGen::noclamp) -- a padding row is the
+// zero point, which need not lie inside the points' box, so the other kinds keep the clamp
+template <bool PLAIN, bool DIAG, bool CLAMP>
 __device__ __forceinline__ void gen_row(const SymGen &gs, const GenCols &gc,
                                         const double *__restrict__ xrow, int r, int lane,
                                         d2 (&ar)[4]) {
   static_assert(!(PLAIN && DIAG), "a diagonal tile is not plain");
+  static_assert(PLAIN || CLAMP, "only a plain tile may drop the clamp");
   const double *xr = xrow + kSymGenMaxD * r;
   double x[kSymGenMaxD];
 #pragma unroll
@@ -249,7 +253,7 @@ __device__ __forceinline__ void gen_row(const SymGen &gs, const GenCols &gc,
     double s = 0.0;
 #pragma unroll
     for (int t = 0; t < kSymGenMaxD; ++t) s = rbf_sqdist_step(s, __dsub_rn(gc.x[j][t], x[t]), t == 0);
-    v[j] = rbf_of_sqdist_lean(s);
+    v[j] = rbf_of_sqdist_lean<CLAMP>(s);
   }
   if constexpr (!PLAIN) {
     const bool rv = gen_row_inside(xrow, r);
@@ -290,7 +294,7 @@ __device__ __forceinline__ void tile_load_batch(const double *A, int64_t rbase, 
 // RB (streaming): the rows held at once.  RB = 4 takes the batch as two half batches, the
 // second loaded (from A) when the first has been used; each row's s0 / s1 chain, its place in
 // the transpose and the row order of acc are those of RB = 8, so the sums are the same bits.
-template <bool GEN, bool PLAIN, bool DIAG, int RB>
+template <bool GEN, bool PLAIN, bool DIAG, int RB, bool CLAMP = true>
 __device__ __forceinline__ void tile_batch(d2 (&a)[GEN ? 1 : RB][4], const double *A,
                                            const SymGen &gs,
                                            const GenCols &gc, const double *xrow,
@@ -303,7 +307,7 @@ __device__ __forceinline__ void tile_batch(d2 (&a)[GEN ? 1 : RB][4], const doubl
   for (int rr = 0; rr < kRB; ++rr) {
     d2 ar[4];
     if constexpr (GEN) {
-      gen_row<PLAIN, DIAG>(gs, gc, xrow, rbase + rr, lane, ar);
+      gen_row<PLAIN, DIAG, CLAMP>(gs, gc, xrow, rbase + rr, lane, ar);
     } else {
       if constexpr (RB < kRB)
         if (rr == RB) tile_load_batch<RB>(A, rbase + RB, lane, a);
@@ -343,8 +347,10 @@ __device__ __forceinline__ void tile_batch(d2 (&a)[GEN ? 1 : RB][4], const doubl
 }
 
 // The wave's batches gb0 + w, gb0 + w + 4, ... of a unit (the first one's entries are already
-// loaded when streaming), and the one uniform branch per unit that picks the generated tile's kind
-template <bool GEN, bool PLAIN, bool DIAG, int RB>
+// loaded when streaming), and the one uniform branch per unit that picks the generated tile's
+// kind and, for a plain tile, the entry's form (gs.noclamp: without the clamp; the clamped plain
+// loop stays an instantiation of its own, so an operator that needs the clamp pays no select)
+template <bool GEN, bool PLAIN, bool DIAG, int RB, bool CLAMP = true>
 __device__ __forceinline__ void tile_batches(d2 (&a)[GEN ? 1 : RB][4], const double *A,
                                              const SymGen &gs, const GenCols &gc, const double *xrow,
                                              bool diag_rt, const d2 (&pc)[4], const double *vrow,
@@ -354,8 +360,8 @@ __device__ __forceinline__ void tile_batches(d2 (&a)[GEN ? 1 : RB][4], const dou
   for (int g = gb0 + w; g < gb1; g += 4) {
     if constexpr (!GEN)
       if (g != gb0 + w) tile_load_batch<RB>(A, g * kRB, lane, a);
-    tile_batch<GEN, PLAIN, DIAG, RB>(a, A, gs, gc, xrow, diag_rt, pc, vrow, g * kRB, lane, red, rows,
-                                     acc);
+    tile_batch<GEN, PLAIN, DIAG, RB, CLAMP>(a, A, gs, gc, xrow, diag_rt, pc, vrow, g * kRB, lane, red,
+                                            rows, acc);
   }
 }
 template <bool GEN, int RB>
@@ -364,7 +370,9 @@ __device__ __forceinline__ void tile_unit(d2 (&a)[GEN ? 1 : RB][4], const double
                                           bool plain, bool diag, const d2 (&pc)[4],
                                           const double *vrow, int gb0, int gb1, int w, int lane,
                                           double *red, double *rows, d2 (&acc)[4]) {
-  if (GEN && plain)
+  if (GEN && plain && gs.noclamp != 0)
+    tile_batches<GEN, GEN, false, RB, !GEN>(a, A, gs, gc, xrow, diag, pc, vrow, gb0, gb1, w, lane, red, rows, acc);
+  else if (GEN && plain)
     tile_batches<GEN, GEN, false, RB>(a, A, gs, gc, xrow, diag, pc, vrow, gb0, gb1, w, lane, red, rows, acc);
   else if (GEN && diag)
     tile_batches<GEN, false, GEN, RB>(a, A, gs, gc, xrow, diag, pc, vrow, gb0, gb1, w, lane, red, rows, acc);
@@ -544,6 +552,10 @@ __device__ __forceinline__ unsigned cu_key() {
 
 // MLFF_SYM_TRACE record of a workgroup: start, end, units taken, 1 | role << 1 | CU key << 2
 constexpr int kTraceWords = 4;
+// ... and, behind the records of all workgroups, the shader clock (clock64) at its start and end
+// stamps: the clock the launch ran at is their difference over that of the wall stamps.  Role
+// kernels only, and a region of its own, so that k_symv_dyn<false> stays as it is
+constexpr int kTraceClockWords = 2;
 
 // ROLES false: every workgroup streams, one counter over all units (sp.gen off: matrices set
 // by the host, MLFF_SYM_GEN=0, d above kSymGenMaxD); the first unit is blockIdx.x, without an
@@ -573,7 +585,11 @@ __global__ __launch_bounds__(256, RB < kRB ? 3 : 1) void k_symv_dyn(const double
   if (status != nullptr && *status != ST_RUNNING) return;
   // MLFF_SYM_TRACE (diagnostic): per workgroup its start, end, units taken, role and CU
   unsigned long long *tr = wgtrace != nullptr ? wgtrace + kTraceWords * blockIdx.x : nullptr;
+  unsigned long long *trc = nullptr;
+  if constexpr (ROLES)
+    if (tr != nullptr) trc = wgtrace + kTraceWords * gridDim.x + kTraceClockWords * blockIdx.x;
   if (tr != nullptr && threadIdx.x == 0) tr[0] = wall_clock64();
+  if (trc != nullptr && threadIdx.x == 0) trc[0] = clock64();
   __shared__ double sh[kTileLds + (ROLES ? kGenRowLds : 0)];
   __shared__ long long s_next;
   __shared__ int s_role;
@@ -621,6 +637,7 @@ __global__ __launch_bounds__(256, RB < kRB ? 3 : 1) void k_symv_dyn(const double
     __syncthreads();
     if (u >= nunits) {
       if (tr != nullptr && threadIdx.x == 0) tr[1] = wall_clock64();
+      if (trc != nullptr && threadIdx.x == 0) trc[1] = clock64();
       return;
     }
   }
@@ -637,6 +654,7 @@ __global__ __launch_bounds__(256, RB < kRB ? 3 : 1) void k_symv_dyn(const double
   if (tr != nullptr && threadIdx.x == 0) {
     tr[1] = wall_clock64();
     tr[2] = (unsigned long long)units_done;
+    if (trc != nullptr) trc[1] = clock64();
   }
 }
 
@@ -1147,23 +1165,28 @@ __global__ __launch_bounds__(256) void k_sym_gen_rbf(const int2 *__restrict__ li
   }
 }
 
-// test hook (mlff_test_rbf_exp): both forms of the entry's exp over an array of squared distances
+// test hook (mlff_test_rbf_exp, mlff_test_rbf_exp_noclamp): the library's exp and one form of the
+// generating role's over an array of squared distances
+template <bool CLAMP>
 __global__ __launch_bounds__(256) void k_rbf_exp_probe(const double *__restrict__ s, int64_t n,
                                                        double *__restrict__ lib_out,
                                                        double *__restrict__ lean_out) {
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     lib_out[i] = rbf_of_sqdist(s[i]);
-    lean_out[i] = rbf_of_sqdist_lean(s[i]);
+    lean_out[i] = rbf_of_sqdist_lean<CLAMP>(s[i]);
   }
 }
 
 }  // namespace
 
-void launch_rbf_exp_probe(const double *s, int64_t n, double *lib_out, double *lean_out,
+void launch_rbf_exp_probe(const double *s, int64_t n, double *lib_out, double *lean_out, bool clamp,
                           hipStream_t st) {
   if (n <= 0) return;
   const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, 4096);
-  hipLaunchKernelGGL(k_rbf_exp_probe, dim3(grid), dim3(256), 0, st, s, n, lib_out, lean_out);
+  if (clamp)
+    hipLaunchKernelGGL(k_rbf_exp_probe<true>, dim3(grid), dim3(256), 0, st, s, n, lib_out, lean_out);
+  else
+    hipLaunchKernelGGL(k_rbf_exp_probe<false>, dim3(grid), dim3(256), 0, st, s, n, lib_out, lean_out);
 }
 
 // The MLFF_SYM_* environment knobs (all A/B or diagnostic; the defaults are the measured
@@ -1208,6 +1231,9 @@ struct SymKnobs {
   // and two generating); 0, the default: three where the operator has kSymThreeWgMinUnits
   // units per workgroup, else two (sym_plan)
   int wgs = 0;
+  // MLFF_SYM_GEN_CLAMP=1: the generating role clamps the squared distance in every tile, also
+  // where the points' extent says it cannot matter (SymGen::noclamp; A/B, tests)
+  bool gen_clamp = false;
   // MLFF_SYM_REDUCE_LIST=0: k_sym_reduce_w instead of k_sym_reduce_wl (W > 1)
   bool reduce_list = true;
   // MLFF_SYM_PQ_ORDERED=1: k_sym_reduce_wl's arrival in the formally ordered form (pq_put)
@@ -1242,6 +1268,7 @@ static SymKnobs sym_knobs() {
     const int v = std::atoi(e);
     if (v == 2 || v == 3) k.wgs = v;
   }
+  if (const char *e = std::getenv("MLFF_SYM_GEN_CLAMP")) k.gen_clamp = std::atoi(e) != 0;
   if (const char *e = std::getenv("MLFF_SYM_REDUCE_LIST")) k.reduce_list = std::atoi(e) != 0;
   if (const char *e = std::getenv("MLFF_SYM_PQ_ORDERED")) k.pq_ordered = std::atoi(e) != 0;
   if (const char *e = std::getenv("MLFF_SYM_TRACE")) k.trace_at = std::atoll(e);
@@ -1249,11 +1276,12 @@ static SymKnobs sym_knobs() {
 }
 
 // MLFF_SYM_TRACE: the ramp until every workgroup runs, the tail after the median one is done
-// (tr: start, end (10-ns ticks), units, role and CU of each of the G workgroups; one sync), and
-// where the dispatcher put the two roles
+// (tr: start, end (10-ns ticks), units, role and CU of each of the G workgroups; one sync),
+// where the dispatcher put the two roles, and (role kernels) the shader clock each role's
+// workgroups ran at: shader ticks over wall ticks between a workgroup's two stamps
 static void print_symv_trace(const unsigned long long *tr, unsigned G, int64_t units, int wgs,
                              hipStream_t s) {
-  std::vector<unsigned long long> h((size_t)kTraceWords * G);
+  std::vector<unsigned long long> h((size_t)(kTraceWords + kTraceClockWords) * G);
   if (hipStreamSynchronize(s) != hipSuccess ||
       hipMemcpy(h.data(), tr, sizeof(unsigned long long) * h.size(), hipMemcpyDeviceToHost) != hipSuccess)
     return;
@@ -1270,6 +1298,7 @@ static void print_symv_trace(const unsigned long long *tr, unsigned G, int64_t u
   std::vector<int> cu_s(kSymCuWords, 0), cu_g(kSymCuWords, 0);
   int xs[16] = {0}, xg[16] = {0};
   double un_s = 0.0, un_g = 0.0;
+  std::vector<double> mhz_s, mhz_g;  // shader clock of the workgroups of either role
   for (unsigned g = 0; g < G; ++g) {
     const unsigned long long *r = &h[(size_t)kTraceWords * g];
     if (r[0] == 0) continue;
@@ -1283,6 +1312,10 @@ static void print_symv_trace(const unsigned long long *tr, unsigned G, int64_t u
     ++(gen ? cu_g : cu_s)[key];
     ++(gen ? xg : xs)[key >> 8];
     (gen ? un_g : un_s) += (double)r[2];
+    // shader ticks per 10-ns wall tick, times 100 MHz
+    const unsigned long long *c = &h[(size_t)kTraceWords * G + (size_t)kTraceClockWords * g];
+    if (c[0] != 0 && c[1] > c[0] && r[1] > r[0])
+      (gen ? mhz_g : mhz_s).push_back(100.0 * (double)(c[1] - c[0]) / (double)(r[1] - r[0]));
   }
   auto q = [](std::vector<double> v, double f) {
     std::sort(v.begin(), v.end());
@@ -1320,6 +1353,11 @@ static void print_symv_trace(const unsigned long long *tr, unsigned G, int64_t u
                "of the span); per XCC id%s\n",
                cus, wgs - 1, paired, wgs, two_s, wgs, two_g, other, un_s, un_g, 1e6 * un_s / span,
                1e6 * un_g / span, per_xcc.c_str());
+  if (!mhz_s.empty() || !mhz_g.empty())
+    std::fprintf(stderr,
+                 "[sym trace] shader clock over a workgroup's life, median per role: stream %.0f MHz "
+                 "(%zu workgroups), gen %.0f MHz (%zu workgroups)\n",
+                 q(mhz_s, 0.5), mhz_s.size(), q(mhz_g, 0.5), mhz_g.size());
 }
 
 void launch_symv(const SymPack &sp, const double *v_full, double *P, const int *status,
@@ -1335,8 +1373,9 @@ void launch_symv(const SymPack &sp, const double *v_full, double *P, const int *
   static const long long trace_at = sym_knobs().trace_at;
   static long long launches = 0;
   DevBuf<unsigned long long> tr;
-  if (trace_at > 0 && ++launches == trace_at && tr.alloc((int64_t)kTraceWords * G) == hipSuccess)
-    (void)hipMemsetAsync(tr, 0, sizeof(unsigned long long) * kTraceWords * G, s);
+  constexpr int kWords = kTraceWords + kTraceClockWords;
+  if (trace_at > 0 && ++launches == trace_at && tr.alloc((int64_t)kWords * G) == hipSuccess)
+    (void)hipMemsetAsync(tr, 0, sizeof(unsigned long long) * kWords * G, s);
   if (sp.gen && sp.rb4)
     hipLaunchKernelGGL((k_symv_dyn<true, 4>), dim3(G), dim3(256), 0, s,
                        sp.tiles, sp.list, v_full, P, sp.Pq, sp.Np, (int)sp.nwhole, (long long)grid,
@@ -1512,8 +1551,10 @@ static SymPlan sym_plan(const mlff_ctx *ctx, const SymKnobs &kn) {
           pl.dyn = (int64_t)occ * cus;
         }
       }
+      // every rank holds the same points, so every rank takes the same decision
+      const bool noclamp = !kn.gen_clamp && ctx->rbf.finite && ctx->rbf.extent2 <= kSymGenNoClampExtent2;
       pl.gsrc = SymGen{ctx->rbf.Xs, ctx->rbf.d, ctx->rbf.jitter, ctx->N, ctx->rows_per, ctx->blk,
-                       (int)n_s, qmode, kn.roles, kn.pool_first, pl.wgs};
+                       (int)n_s, qmode, kn.roles, kn.pool_first, pl.wgs, noclamp ? 1 : 0};
     }
   }
   return pl;

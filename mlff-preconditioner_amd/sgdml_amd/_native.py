@@ -72,6 +72,7 @@ SIGNATURES = {
     "mlff_sgdml_energies": (_int, [_c_ctx, _p_dbl, _p_dbl, _p_i64, _p_i64]),
     "mlff_sgdml_descriptors": (_int, [_p_dbl, _i64, _int, _p_dbl, _p_dbl]),
     "mlff_test_rbf_exp": (_int, [_c_ctx, _p_dbl, _i64, _p_dbl, _p_dbl]),
+    "mlff_test_rbf_exp_noclamp": (_int, [_c_ctx, _p_dbl, _i64, _p_dbl, _p_dbl]),
     "mlff_predict_set_model": (_int, [_c_ctx, _p_dbl, _p_dbl, _i64, _int, _p_i32, _int, _dbl, _dbl,
                                       _dbl]),
     "mlff_predict_set_energy_coefficients": (_int, [_c_ctx, _p_dbl]),
@@ -85,6 +86,7 @@ SIGNATURES = {
     "mlff_set_storage": (_int, [_c_ctx, _int]),
     "mlff_storage_info": (_int, [_c_ctx, _p_int, _p_dbl]),
     "mlff_sym_launch_info": (_int, [_c_ctx, _p_int, _p_i64]),
+    "mlff_sym_gen_info": (_int, [_c_ctx, _p_int, _p_dbl]),
     "mlff_operator_form": (_int, [_c_ctx, _p_int]),
     "mlff_precon_none": (_int, [_c_ctx]),
     "mlff_precon_pivchol": (_int, [_c_ctx, _i64, _int, _p_i64, _p_dbl]),

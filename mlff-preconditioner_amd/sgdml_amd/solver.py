@@ -278,6 +278,14 @@ class KernelSolver:
         self._call("mlff_sym_launch_info", ctypes.byref(wgs), ctypes.byref(grid))
         return wgs.value, grid.value
 
+    def sym_gen_info(self) -> tuple[bool, float]:
+        """(the generating role of the symmetric tile mat-vec evaluates plain tiles without the
+        clamp of the squared distance, squared diagonal of the scaled points' bounding box)."""
+        noclamp = ctypes.c_int()
+        extent2 = ctypes.c_double()
+        self._call("mlff_sym_gen_info", ctypes.byref(noclamp), ctypes.byref(extent2))
+        return bool(noclamp.value), extent2.value
+
     def operator_form(self) -> str | None:
         """Form of the matrix-free sGDML operator: 'pair', 'rec' (record-factored, many atoms /
         few points) or 'pt' (pair-tile, few atoms / many points); None without one."""
