@@ -306,6 +306,22 @@ int mlff_predict_hessian(mlff_ctx *ctx, const double *R, int64_t Q, double *H_ou
  * supplies dE / d descriptor), and bytes of the two streams of the training rows (derivation at
  * pred_hess_work, csrc/kernels_predict_hess.hip).  No reference counterpart (measurement). */
 int mlff_predict_hessian_info(mlff_ctx *ctx, double *flops_per_query_out, double *bytes_per_query_out);
+/* Hessian-vector products of the model set by mlff_predict_set_model (with the energy
+ * coefficients, if any), the Hessian never formed: R is Q x n_atoms x 3, V and HV_out are
+ * Q x K x 3 n_atoms, HV_out[q][k] = H(R_q) V[q][k] with H the matrix mlff_predict_hessian returns
+ * (same units, std included).  No reference counterpart; the formulas are at the head of
+ * csrc/kernels_predict_hvp.hip.  The K vectors of a query share every training row loaded and
+ * its row scalars.  The bits of HV_out[q][k] do not depend on Q, on K, or on the position of q
+ * and k in the call.  There is no limit on the number of atoms.  The slab buffers are allocated
+ * by the first call (MLFF_ERR_NOMEM if they cannot be; MLFF_PRED_SLAB bounds the queries per pass
+ * here too).  MLFF_ERR_ARG before a model is set and for Q < 0 or K < 0; Q = 0 or K = 0 is
+ * MLFF_OK and touches nothing. */
+int mlff_predict_hvp(mlff_ctx *ctx, const double *R, const double *V, int64_t Q, int64_t K, double *HV_out);
+/* The algorithmic work of mlff_predict_hvp: flops of one product computed alone (Q = K = 1; the
+ * vectors of a block share more than half of it) and the bytes of training rows one block of
+ * vectors of a query streams (derivation at pred_hvp_work, csrc/kernels_predict_hvp.hip).  No
+ * reference counterpart (measurement). */
+int mlff_predict_hvp_info(mlff_ctx *ctx, double *flops_per_product_out, double *bytes_per_query_out);
 
 int mlff_set_operator(mlff_ctx *ctx, double sigma_K, double lam);
 /* y_local = A v_global (v_global has N entries).  Collective over the ranks

@@ -1452,6 +1452,34 @@ int mlff_predict_hessian_info(mlff_ctx *ctx, double *flops_per_query_out, double
   MLFF_API_END(ctx)
 }
 
+int mlff_predict_hvp(mlff_ctx *ctx, const double *R, const double *V, int64_t Q, int64_t K, double *HV_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  if (ctx->world > 1) return set_error(ctx, MLFF_ERR_ARG, "predict hvp: runs on a one-rank context");
+  if (!ctx->pred.ready)
+    return set_error(ctx, MLFF_ERR_ARG, "predict hvp: no model set (mlff_predict_set_model)");
+  if (Q < 0) return set_error(ctx, MLFF_ERR_ARG, "predict hvp: Q < 0");
+  if (K < 0) return set_error(ctx, MLFF_ERR_ARG, "predict hvp: K < 0");
+  if (Q == 0 || K == 0) return MLFF_OK;
+  if (R == nullptr || V == nullptr || HV_out == nullptr)
+    return set_error(ctx, MLFF_ERR_ARG, "predict hvp: null pointer");
+  return pred_hvp_run(ctx, R, V, Q, K, HV_out);
+  MLFF_API_END(ctx)
+}
+
+int mlff_predict_hvp_info(mlff_ctx *ctx, double *flops_per_product_out, double *bytes_per_query_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  if (!ctx->pred.ready)
+    return set_error(ctx, MLFF_ERR_ARG, "predict hvp: no model set (mlff_predict_set_model)");
+  double fl = 0.0, by = 0.0;
+  pred_hvp_work(ctx->pred, &fl, &by);
+  if (flops_per_product_out) *flops_per_product_out = fl;
+  if (bytes_per_query_out) *bytes_per_query_out = by;
+  return MLFF_OK;
+  MLFF_API_END(ctx)
+}
+
 int mlff_set_operator(mlff_ctx *ctx, double sigma_K, double lam) {
   MLFF_API_BEGIN
   MLFF_ENTER(ctx);

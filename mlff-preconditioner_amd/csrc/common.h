@@ -301,6 +301,20 @@ struct PredData {
     DevBuf<double> H;                      // slab x 3n x 3n
     PinBuf<double> h_out;                  // pinned staging of H
   } hs;
+  // Hessian-vector products (kernels_predict_hvp.hip): allocated by the first mlff_predict_hvp;
+  // hv = Hvp{} releases them
+  struct Hvp {
+    bool ready = false;
+    int S = 1;                             // chunks of the (j, p) range: fixed by MP, D and the form
+    int64_t slab = 0;                      // queries per pass (<= the prediction's slab)
+    int64_t PS = 0;                        // row of the partials of a full vector block
+    DevBuf<double> V, Y;                   // a pass's geometries (slab x 3n) then its vectors (slab x
+                                           // kHvPass x 3n); slab x kHvPass x D: J v
+    DevBuf<double> part;                   // S x (slab x blocks of a pass) x PS chunk partials
+    DevBuf<double> sum;                    // (slab x blocks of a pass) x PS
+    DevBuf<double> HV;                     // slab x kHvPass x 3n
+    PinBuf<double> h_v, h_out;             // pinned staging of V (geometries included) and HV
+  } hv;
 };
 
 // Low-rank preconditioner z = sigma_p / lam (r - T^T T r): the panel, the form of its apply and
@@ -1116,6 +1130,12 @@ int pred_fd_slab(mlff_ctx *ctx, const double *R, int64_t nq, bool with_fd);
 // (MLFF_PRED_HESS_SLAB is read there)
 int pred_hess_run(mlff_ctx *ctx, const double *R, int64_t Q, double *H_out);
 void pred_hess_work(const PredData &pd, double *flops_per_query, double *bytes_per_query);
+
+// ---- Hessian-vector products of the held model (kernels_predict_hvp.hip) ------
+// HV (Q x K x 3n) = H(R_q) V[q][k] of the Q host geometries R and their K vectors each, H never
+// formed; the slab buffers are allocated by the first call
+int pred_hvp_run(mlff_ctx *ctx, const double *R, const double *V, int64_t Q, int64_t K, double *HV_out);
+void pred_hvp_work(const PredData &pd, double *flops_per_product, double *bytes_per_query);
 
 // ---- operator access for the builds and the PCG driver (api.hip) --------------
 // require the operator and resolve its storage (builds the tiles if they are to be used)

@@ -250,6 +250,31 @@ class KernelSolver:
         self._call("mlff_predict_hessian_info", ctypes.byref(fl), ctypes.byref(by))
         return fl.value, by.value
 
+    def predict_hvp(self, R: np.ndarray, V: np.ndarray) -> np.ndarray:
+        """HV (Q, K, 3 n_atoms), HV[q, k] = H(R_q) V[q, k] with H the matrix `predict_hessian`
+        returns, never formed (mlff_predict_hvp; the reference has none).  R: Q x n_atoms x 3,
+        V: Q x K x 3 n_atoms.  No limit on the number of atoms."""
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        n = getattr(self, "_pred_n_atoms", None)
+        if n is not None and (R.ndim != 3 or R.shape[1:] != (n, 3)):
+            raise ValueError(f"R must be Q x {n} x 3, got {R.shape}")
+        if n is None and (R.ndim != 3 or R.shape[2] != 3):
+            raise ValueError("R must be Q x n_atoms x 3")
+        Q, n = R.shape[0], R.shape[1]
+        if V.ndim != 3 or V.shape[0] != Q or V.shape[2] != 3 * n:
+            raise ValueError(f"V must be {Q} x K x {3 * n}, got {V.shape}")
+        HV = np.empty(V.shape)
+        self._call("mlff_predict_hvp", nat.dptr(R), nat.dptr(V), int(Q), int(V.shape[1]), nat.dptr(HV))
+        return HV
+
+    def predict_hvp_info(self) -> tuple[float, float]:
+        """(flops of one product computed alone, bytes of training rows one query streams) of
+        `predict_hvp` (mlff_predict_hvp_info)."""
+        fl, by = ctypes.c_double(), ctypes.c_double()
+        self._call("mlff_predict_hvp_info", ctypes.byref(fl), ctypes.byref(by))
+        return fl.value, by.value
+
     def set_operator(self, sigma_K: float, lam: float):
         self._call("mlff_set_operator", float(sigma_K), float(lam))
 
