@@ -323,6 +323,37 @@ int mlff_predict_hvp(mlff_ctx *ctx, const double *R, const double *V, int64_t Q,
  * reference counterpart (measurement). */
 int mlff_predict_hvp_info(mlff_ctx *ctx, double *flops_per_product_out, double *bytes_per_query_out);
 
+/* Molecular dynamics with the model set by mlff_predict_set_model (with the energy coefficients,
+ * if any), the trajectory kept on the device: Q independent replicas from the positions R0 and
+ * velocities V0 (both Q x 3 n_atoms), n_steps steps of synchronous velocity Verlet,
+ *   v += h_i F;  R += dt v;  E, F = the model at R;  v += h_i F,
+ * with h (n_atoms) = (dt acc_unit / 2) / m_i formed by the caller and every product rounded before
+ * its sum (no fma).  E and F are mlff_predict's, bit for bit, so a host loop over mlff_predict
+ * with these updates reproduces a run exactly; a replica's bits do not depend on Q, on its
+ * position, on the slab, on the frame capacity or on the form.  T = n_steps / stride + 1 frames
+ * are written, those of the steps 0, stride, ..., n_steps: R_out, V_out and F_out (want_forces
+ * != 0; else F_out may be NULL) are Q x T x 3 n_atoms, E_out is Q x T; a frame holds R, V, E(R)
+ * and F(R) of one instant.  Between frame flushes there is no host copy and no stream
+ * synchronisation: frames collect in a device buffer (256 MB for a full slab, at least 2 frames;
+ * MLFF_MD_FRAMES overrides the count) that is copied out when full and at the end.  The work
+ * buffers are allocated by the first call (MLFF_ERR_NOMEM if they cannot be).  A replica whose
+ * atoms coincide or whose values overflow returns non-finite frames and disturbs no other.  No
+ * reference counterpart; csrc/kernels_md.hip.  MLFF_ERR_STATE before a model is set;
+ * MLFF_ERR_ARG for null pointers, Q < 0, n_steps < 0, stride < 1, n_steps % stride != 0 or a dt
+ * that is not finite.  Q = 0 is MLFF_OK; n_steps = 0 gives the one frame of the start. */
+int mlff_md_run(mlff_ctx *ctx, const double *R0, const double *V0, const double *h, int64_t Q, double dt,
+                int64_t n_steps, int64_t stride, int want_forces, double *R_out, double *V_out,
+                double *E_out, double *F_out);
+/* How mlff_md_run runs: the kernel launches one step takes (2 or 4), the frames its device buffer
+ * holds and the stream synchronisations the last run made (one per flush of that buffer).
+ * MLFF_ERR_STATE before a model is set.  No reference counterpart (measurement). */
+int mlff_md_info(mlff_ctx *ctx, int *launches_per_step_out, int64_t *frame_capacity_out,
+                 int64_t *syncs_last_run_out);
+/* The form of mlff_md_run's step: 0 the default, 4 (any model) or 2 (tile models, D <= 288) launches
+ * per step; the same bits either way.  Reset by mlff_predict_set_model.  MLFF_ERR_STATE before a
+ * model is set, MLFF_ERR_ARG for a form the model does not have. */
+int mlff_md_set_form(mlff_ctx *ctx, int launches_per_step);
+
 int mlff_set_operator(mlff_ctx *ctx, double sigma_K, double lam);
 /* y_local = A v_global (v_global has N entries).  Collective over the ranks
  * when the symmetric tiled storage is in use (a reduce-scatter of the partial

@@ -1480,6 +1480,42 @@ int mlff_predict_hvp_info(mlff_ctx *ctx, double *flops_per_product_out, double *
   MLFF_API_END(ctx)
 }
 
+int mlff_md_run(mlff_ctx *ctx, const double *R0, const double *V0, const double *h, int64_t Q, double dt,
+                int64_t n_steps, int64_t stride, int want_forces, double *R_out, double *V_out,
+                double *E_out, double *F_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  if (ctx->world > 1) return set_error(ctx, MLFF_ERR_ARG, "md: runs on a one-rank context");
+  if (!ctx->pred.ready) return set_error(ctx, MLFF_ERR_STATE, "md: no model set (mlff_predict_set_model)");
+  if (Q < 0) return set_error(ctx, MLFF_ERR_ARG, "md: Q < 0");
+  if (n_steps < 0) return set_error(ctx, MLFF_ERR_ARG, "md: n_steps < 0");
+  if (stride < 1) return set_error(ctx, MLFF_ERR_ARG, "md: stride < 1");
+  if (n_steps % stride != 0) return set_error(ctx, MLFF_ERR_ARG, "md: n_steps is not a multiple of stride");
+  if (!std::isfinite(dt)) return set_error(ctx, MLFF_ERR_ARG, "md: dt is not finite");
+  if (Q > 0 && (R0 == nullptr || V0 == nullptr || h == nullptr || R_out == nullptr || V_out == nullptr ||
+                E_out == nullptr || (want_forces != 0 && F_out == nullptr)))
+    return set_error(ctx, MLFF_ERR_ARG, "md: null pointer");
+  return md_run(ctx, R0, V0, h, Q, dt, n_steps, stride, want_forces != 0, R_out, V_out, E_out, F_out);
+  MLFF_API_END(ctx)
+}
+
+int mlff_md_info(mlff_ctx *ctx, int *launches_per_step_out, int64_t *frame_capacity_out,
+                 int64_t *syncs_last_run_out) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  if (!ctx->pred.ready) return set_error(ctx, MLFF_ERR_STATE, "md: no model set (mlff_predict_set_model)");
+  return md_info(ctx, launches_per_step_out, frame_capacity_out, syncs_last_run_out);
+  MLFF_API_END(ctx)
+}
+
+int mlff_md_set_form(mlff_ctx *ctx, int launches_per_step) {
+  MLFF_API_BEGIN
+  MLFF_ENTER(ctx);
+  if (!ctx->pred.ready) return set_error(ctx, MLFF_ERR_STATE, "md: no model set (mlff_predict_set_model)");
+  return md_set_form(ctx, launches_per_step);
+  MLFF_API_END(ctx)
+}
+
 int mlff_set_operator(mlff_ctx *ctx, double sigma_K, double lam) {
   MLFF_API_BEGIN
   MLFF_ENTER(ctx);

@@ -315,6 +315,19 @@ struct PredData {
     DevBuf<double> HV;                     // slab x kHvPass x 3n
     PinBuf<double> h_v, h_out;             // pinned staging of V (geometries included) and HV
   } hv;
+  // Molecular dynamics (kernels_md.hip): configured and allocated by the first mlff_md_run;
+  // md = Md{} releases it
+  struct Md {
+    bool ready = false;
+    int launches = 4;                      // launches per step of the form in use (2: tile models)
+    int want = 0;                          // 0: the default form, 2 / 4: asked for (mlff_md_set_form)
+    int64_t cap = 0;                       // frames the device frame buffer holds (MLFF_MD_FRAMES)
+    int64_t syncs = 0;                     // stream synchronisations of the last run
+    int64_t frame_len = 0;                 // doubles the frame buffers hold
+    DevBuf<double> hV;                     // h (n) then the slab's velocities (slab x 3n)
+    DevBuf<double> frames;                 // cap frames of the slab: replica rows R, V, E (, F)
+    PinBuf<double> h_in, h_frames;         // pinned staging of R0 / h, V0 and of the frames
+  } md;
 };
 
 // Low-rank preconditioner z = sigma_p / lam (r - T^T T r): the panel, the form of its apply and
@@ -1124,6 +1137,22 @@ void pred_work(const PredData &pd, double *flops_per_query, double *bytes_per_qu
 // chunk-sum stages: pred.Rq, Rdq, Rddq (and Fd) of those queries are then on the device (in
 // stream order)
 int pred_fd_slab(mlff_ctx *ctx, const double *R, int64_t nq, bool with_fd);
+// the stages of pred_fd_slab for the nq geometries already in pred.Rq, on stream s: any of the
+// descriptors, the pair stage and the chunk sum, launched in this order
+enum : int { kPrStageDesc = 1, kPrStagePair = 2, kPrStageSum = 4, kPrStageAll = 7 };
+void pr_launch_fd(const PredData &pd, int64_t nq, int stages, hipStream_t s);
+
+// ---- molecular dynamics with the held model (kernels_md.hip) ------------------
+// n_steps velocity-Verlet steps of Q replicas; the work buffers are allocated by the first call
+// (MLFF_MD_FRAMES is read there)
+int md_run(mlff_ctx *ctx, const double *R0, const double *V0, const double *h, int64_t Q, double dt,
+           int64_t n_steps, int64_t stride, bool want_forces, double *R_out, double *V_out,
+           double *E_out, double *F_out);
+// launches per step of the form a run would use, the frame capacity, the synchronisations of the
+// last run; configures (no allocation) where no run has
+int md_info(mlff_ctx *ctx, int *launches_per_step, int64_t *frame_capacity, int64_t *syncs_last_run);
+// 0: the default form, 2 / 4: that many launches per step (2 needs a tile model)
+int md_set_form(mlff_ctx *ctx, int launches);
 
 // ---- Hessians of the held model (kernels_predict_hess.hip) -------------------
 // H (Q x 3n x 3n) of the Q host geometries R; the slab buffers are allocated by the first call

@@ -371,11 +371,11 @@ __global__ __launch_bounds__(256) void k_pr_sum(const double *__restrict__ part,
   if (e < D)
     Fd[q * D + e] = fsum;
   else
-    E[q] = __dadd_rn(__dmul_rn(fsum, std), cint);  // E_F *= std; E = E_F[:, 0] + c
+    E[q] = pred_energy(fsum, std, cint);
 }
 
 // F[q][3 at + c] = std sum_b (+-) Rdd_q[pair(at, b)][c] Fd_q[pair(at, b)], partners b in
-// increasing order: one thread per row
+// increasing order (jt_row, sgdml_pair.h): one thread per row
 __global__ __launch_bounds__(64) void k_pr_jt(const double *__restrict__ Rdd,
                                               const double *__restrict__ Fd, int n, int64_t D,
                                               double std, double *__restrict__ F) {
@@ -383,27 +383,7 @@ __global__ __launch_bounds__(64) void k_pr_jt(const double *__restrict__ Rdd,
   if (r >= 3 * n) return;
   const int64_t q = blockIdx.y;
   const int at = r / 3, c = r % 3;
-  const double *jr = Rdd + q * D * 3 + c;
-  const double *fr = Fd + q * D;
-  // batches of 8 partners: their loads in flight together, the fmas in partner order (the
-  // partner b == at is skipped by a zero Jacobian entry: fma(0, f, acc) leaves acc as it is)
-  double acc = 0.0;
-  for (int b0 = 0; b0 < n; b0 += 8) {
-    double rv[8], fv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int b = b0 + u;
-      const bool ok = b < n && b != at;
-      const int64_t d = ok ? pair_idx(at, b) : 0;
-      const double v = ok ? jr[d * 3] : 0.0;
-      rv[u] = at > b ? -v : v;
-      fv[u] = ok ? fr[d] : 0.0;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (b0 + u < n && b0 + u != at) acc = fma(rv[u], fv[u], acc);
-  }
-  F[q * 3 * n + r] = std * acc;
+  F[q * 3 * n + r] = std * jt_row(Rdd + q * D * 3 + c, Fd + q * D, n, at);
 }
 
 using PrFn = void (*)(PrArgs);
@@ -552,9 +532,9 @@ static PrArgs pr_model_args(const PredData &pd) {
   return a;
 }
 
-// descriptors of the nq queries in pd.Rq (Rdq, Rddq of the slab) and, with_fd, the pair stage
-// and the chunk sum (Fd of the slab)
-static void pr_launch_fd(const PredData &pd, int64_t nq, bool with_fd, hipStream_t s) {
+// the stages in `stages` (kPrStage*, common.h) for the nq queries of the slab, in this order:
+// descriptors of the geometries in pd.Rq (Rdq, Rddq), the pair stage (part), the chunk sum (Fd, E)
+void pr_launch_fd(const PredData &pd, int64_t nq, int stages, hipStream_t s) {
   const int64_t D = pd.D;
   PrArgs a = pr_model_args(pd);
   a.Rdq = pd.Rdq;
@@ -565,20 +545,21 @@ static void pr_launch_fd(const PredData &pd, int64_t nq, bool with_fd, hipStream
   a.ecol = pd.ecol;
   const bool ecstr = pd.Et != nullptr;
   const unsigned gx = (unsigned)std::min<int64_t>((D + 255) / 256, 64);
-  hipLaunchKernelGGL(k_pr_desc, dim3(gx, (unsigned)nq), dim3(256), 0, s, pd.Rq, pd.n, pd.Rdq, pd.Rddq);
-  if (!with_fd) return;
-  if (pd.form == 0) {
+  if (stages & kPrStageDesc)
+    hipLaunchKernelGGL(k_pr_desc, dim3(gx, (unsigned)nq), dim3(256), 0, s, pd.Rq, pd.n, pd.Rdq, pd.Rddq);
+  if ((stages & kPrStagePair) && pd.form == 0) {
     const PrVariant *v = pr_variant(D);
     hipLaunchKernelGGL(ecstr ? v->fn_e : v->fn,
                        dim3((unsigned)((nq + pd.G - 1) / pd.G), (unsigned)pd.S), dim3(kPrThreads),
                        0, s, a);
-  } else {
+  } else if (stages & kPrStagePair) {
     hipLaunchKernelGGL(ecstr ? k_pr_stream<true> : k_pr_stream<false>,
                        dim3((unsigned)((nq + kPrQB - 1) / kPrQB), (unsigned)pd.S), dim3(256), 0, s,
                        a);
   }
-  hipLaunchKernelGGL(k_pr_sum, dim3((unsigned)((D + 1 + kSumE - 1) / kSumE), (unsigned)nq),
-                     dim3(256), 0, s, pd.part, pd.PS, pd.ecol, D, nq, pd.S, pd.std, pd.c, pd.Fd, pd.EF);
+  if (stages & kPrStageSum)
+    hipLaunchKernelGGL(k_pr_sum, dim3((unsigned)((D + 1 + kSumE - 1) / kSumE), (unsigned)nq),
+                       dim3(256), 0, s, pd.part, pd.PS, pd.ecol, D, nq, pd.S, pd.std, pd.c, pd.Fd, pd.EF);
 }
 
 int pred_fd_slab(mlff_ctx *ctx, const double *R, int64_t nq, bool with_fd) {
@@ -588,7 +569,7 @@ int pred_fd_slab(mlff_ctx *ctx, const double *R, int64_t nq, bool with_fd) {
   // through the pinned staging buffer: one asynchronous copy per slab
   std::memcpy(pd.h_in, R, sizeof(double) * nq * n3);
   MLFF_HIP(ctx, hipMemcpyAsync(pd.Rq, pd.h_in, sizeof(double) * nq * n3, hipMemcpyHostToDevice, s));
-  pr_launch_fd(pd, nq, with_fd, s);
+  pr_launch_fd(pd, nq, with_fd ? kPrStageAll : kPrStageDesc, s);
   MLFF_HIP(ctx, hipGetLastError());
   return MLFF_OK;
 }

@@ -1,6 +1,6 @@
 // What the sGDML kernel families share, one copy each: the descriptor-pair index and its inversion,
 // the Matern 5/2 constants and row scalars of the pair-tile family (operator, prediction, Hessians),
-// the descriptor kernel, the fixed-order sum of chunk partials.  The bit guarantees (alphas_E = 0
+// the descriptor kernel, the fixed-order sum of chunk partials, the rows of J^T Fd.  The bit guarantees (alphas_E = 0
 // gives the unconstrained bits, the Hessian's fused Fd equals the prediction's) hold because every
 // user rounds through these functions.  __forceinline__ with arithmetic arguments by value: that
 // shape left the compiled code of the tuned kernels as it was (profiles/sgdml_shared/README.txt,
@@ -104,12 +104,10 @@ __global__ __launch_bounds__(256) void k_desc_t(const double *__restrict__ R, in
 }
 
 constexpr int kSumE = 16, kSumG = 16;  // entries per workgroup of 256 threads, chunk groups
-// Thread (el = tid % kSumE, g = tid / kSumE): group g adds the chunks [S g / 16, S (g + 1) / 16) of
-// its entry in chunk order (src: the entry in chunk 0, zs: the chunk stride; batches of 8 predicated
-// loads in flight); group 0 then adds the group sums in group order and returns the sum (others: 0)
-__device__ __forceinline__ double chunk_sum(const double *__restrict__ src, int64_t zs, int S, bool ok) {
-  __shared__ double sP[kSumG][kSumE];
-  const int el = threadIdx.x % kSumE, g = threadIdx.x / kSumE;
+// The sum of group g < kSumG of an entry: its chunks [S g / 16, S (g + 1) / 16) in chunk order
+// (src: the entry in chunk 0, zs: the chunk stride; batches of 8 predicated loads in flight)
+__device__ __forceinline__ double chunk_group_sum(const double *__restrict__ src, int64_t zs, int S, bool ok,
+                                                  int g) {
   const int z0 = (int)(((int64_t)S * g) / kSumG), z1 = (int)(((int64_t)S * (g + 1)) / kSumG);
   double sum = 0.0;
   for (int z = z0; z < z1; z += 8) {
@@ -119,12 +117,54 @@ __device__ __forceinline__ double chunk_sum(const double *__restrict__ src, int6
 #pragma unroll
     for (int u = 0; u < 8; ++u) sum += t[u];
   }
-  sP[g][el] = sum;
-  __syncthreads();
-  if (g != 0 || !ok) return 0.0;
+  return sum;
+}
+// the group sums sP[0 .. kSumG)[el] of an entry in group order
+__device__ __forceinline__ double chunk_groups_total(const double (*sP)[kSumE], int el) {
   double fsum = sP[0][el];
   for (int h = 1; h < kSumG; ++h) fsum += sP[h][el];
   return fsum;
+}
+// The sum of the S chunk partials of an entry, by a workgroup of 256: thread (el = tid % kSumE,
+// g = tid / kSumE) forms the sum of group g of its entry (chunk_group_sum), then group 0 adds the
+// group sums in group order and returns the sum (others: 0)
+__device__ __forceinline__ double chunk_sum(const double *__restrict__ src, int64_t zs, int S, bool ok) {
+  __shared__ double sP[kSumG][kSumE];
+  const int el = threadIdx.x % kSumE, g = threadIdx.x / kSumE;
+  sP[g][el] = chunk_group_sum(src, zs, S, ok, g);
+  __syncthreads();
+  if (g != 0 || !ok) return 0.0;
+  return chunk_groups_total(sP, el);
+}
+
+// E = std E_q + c from the summed energy partial (predict.py:1106-1108: E_F *= std; E = E_F[:, 0] + c)
+__device__ __forceinline__ double pred_energy(double esum, double std, double cint) {
+  return __dadd_rn(__dmul_rn(esum, std), cint);
+}
+
+// Row 3 at + c of J^T Fd: sum_b (+-) Rdd[pair(at, b)][c] Fd[pair(at, b)], partners b in increasing
+// order (jr: the geometry's Rdd + c, fr: its Fd).  Batches of 8 partners: their loads in flight
+// together, the fmas in partner order (the partner b == at is skipped by a zero Jacobian entry:
+// fma(0, f, acc) leaves acc as it is)
+__device__ __forceinline__ double jt_row(const double *__restrict__ jr, const double *__restrict__ fr,
+                                         int n, int at) {
+  double acc = 0.0;
+  for (int b0 = 0; b0 < n; b0 += 8) {
+    double rv[8], fv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int b = b0 + u;
+      const bool ok = b < n && b != at;
+      const int64_t d = ok ? pair_idx(at, b) : 0;
+      const double v = ok ? jr[d * 3] : 0.0;
+      rv[u] = at > b ? -v : v;
+      fv[u] = ok ? fr[d] : 0.0;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (b0 + u < n && b0 + u != at) acc = fma(rv[u], fv[u], acc);
+  }
+  return acc;
 }
 
 }  // namespace mlff

@@ -82,6 +82,10 @@ SIGNATURES = {
     "mlff_predict_hessian_info": (_int, [_c_ctx, _p_dbl, _p_dbl]),
     "mlff_predict_hvp": (_int, [_c_ctx, _p_dbl, _p_dbl, _i64, _i64, _p_dbl]),
     "mlff_predict_hvp_info": (_int, [_c_ctx, _p_dbl, _p_dbl]),
+    "mlff_md_run": (_int, [_c_ctx, _p_dbl, _p_dbl, _p_dbl, _i64, _dbl, _i64, _i64, _int, _p_dbl, _p_dbl,
+                           _p_dbl, _p_dbl]),
+    "mlff_md_info": (_int, [_c_ctx, _p_int, _p_i64, _p_i64]),
+    "mlff_md_set_form": (_int, [_c_ctx, _int]),
     "mlff_set_operator": (_int, [_c_ctx, _dbl, _dbl]),
     "mlff_matvec": (_int, [_c_ctx, _p_dbl, _p_dbl]),
     "mlff_get_diag": (_int, [_c_ctx, _p_dbl]),

@@ -18,9 +18,14 @@ guarantees (`mlff_predict_hessian`, csrc/kernels_predict_hess.hip); the referenc
 `gdml.hessian_vector(R, V)` returns the products of that matrix with one or K vectors per
 geometry without forming it (`mlff_predict_hvp`, csrc/kernels_predict_hvp.hip), for any number of
 atoms.
+
+`gdml.md(R0, V0, masses, dt, steps)` runs velocity-Verlet trajectories of Q independent replicas
+with positions, velocities and forces kept on the device for the whole run (`mlff_md_run`,
+csrc/kernels_md.hip); the recorded frames equal, bit for bit, those of a host loop over `predict`.
 """
 from __future__ import annotations
 
+import operator
 import os
 import threading
 
@@ -139,6 +144,63 @@ def normalize_geometries(R, n_atoms: int) -> np.ndarray:
     else:
         raise ValueError(f"R must be Q x {n3}, Q x {n_atoms} x 3, {n3} or {n_atoms} x 3; got {R.shape}")
     return np.ascontiguousarray(R)
+
+
+# Angstrom fs^-2 per kcal mol^-1 Angstrom^-1 amu^-1: 4184 J/mol over 1e-10 m over 1e-3 kg/mol is
+# 4.184e16 m s^-2 = 4.184e-4 Angstrom fs^-2
+ACC_KCAL_MOL_A_AMU_FS = 4.184e-4
+
+
+def normalize_md_inputs(R0, V0, masses, dt, steps, stride, n_atoms: int):
+    """The inputs of `GDMLPredict.md`, checked on the host: (R0 as Q x n x 3, V0 as Q x 3n, masses
+    (n,), dt, steps, stride).  R0: the shapes `predict` accepts; V0: Q x 3n, Q x n x 3 or, for one
+    geometry, 3n / n x 3; masses finite and > 0; dt finite; steps >= 0 a multiple of stride >= 1.
+    ValueError otherwise."""
+    R = normalize_geometries(R0, n_atoms)
+    Q, n3 = R.shape[0], 3 * n_atoms
+    V = np.asarray(V0, dtype=np.float64)
+    if V.shape in ((Q, n3), (Q, n_atoms, 3)) or (Q == 1 and V.shape in ((n3,), (n_atoms, 3))):
+        V = np.ascontiguousarray(V.reshape(Q, n3))
+    else:
+        raise ValueError(f"V0 must be {Q} x {n3} or {Q} x {n_atoms} x 3 for these {Q} geometries "
+                         f"(or {n3} / {n_atoms} x 3 for one); got {V.shape}")
+    m = np.asarray(masses, dtype=np.float64)
+    if m.shape != (n_atoms,):
+        raise ValueError(f"masses must have shape ({n_atoms},), got {m.shape}")
+    if not (np.all(np.isfinite(m)) and np.all(m > 0)):
+        raise ValueError("masses must be finite and > 0")
+    try:
+        dt = float(dt)
+    except (TypeError, ValueError):
+        raise ValueError(f"dt must be a number, got {dt!r}") from None
+    if not np.isfinite(dt):
+        raise ValueError(f"dt must be finite, got {dt}")
+    try:
+        steps, stride = operator.index(steps), operator.index(stride)
+    except TypeError:
+        raise ValueError(f"steps and stride must be integers, got {steps!r}, {stride!r}") from None
+    if steps < 0:
+        raise ValueError(f"steps must be >= 0, got {steps}")
+    if stride < 1:
+        raise ValueError(f"stride must be >= 1, got {stride}")
+    if steps % stride != 0:
+        raise ValueError(f"steps must be a multiple of stride, got {steps} and {stride}")
+    return R, V, np.ascontiguousarray(m), dt, steps, stride
+
+
+def kinetic_energy(V, masses, acc_unit: float = ACC_KCAL_MOL_A_AMU_FS) -> np.ndarray:
+    """0.5 sum_i m_i |v_i|^2 / acc_unit of every frame, in the model's energy unit, on the host.
+    V: (..., n, 3) or (..., 3n), as `md` returns it; the result has the leading shape (float64;
+    long double where V or the masses are)."""
+    wide = any(np.asarray(a).dtype == np.longdouble for a in (V, masses))  # an oracle's frames
+    m = np.asarray(masses, dtype=np.longdouble if wide else np.float64)
+    V = np.asarray(V, dtype=m.dtype)
+    n = m.size
+    if V.ndim >= 2 and V.shape[-2:] == (n, 3):
+        V = V.reshape(V.shape[:-2] + (3 * n,))
+    elif V.ndim < 1 or V.shape[-1] != 3 * n:
+        raise ValueError(f"V must end in {n} x 3 or {3 * n}, got {V.shape}")
+    return 0.5 * np.sum(np.repeat(m, 3) * V * V, axis=-1) / acc_unit
 
 
 def split_blocks(Q: int, parts: int) -> list[tuple[int, int]]:
@@ -262,6 +324,57 @@ class GDMLPredict:
             HV = np.concatenate(self._all(
                 lambda r: self._engines[r].predict_hvp(R[blocks[r][0]:blocks[r][1]], V[blocks[r][0]:blocks[r][1]])))
         return HV[:, 0] if single else HV
+
+    def md(self, R0, V0, masses, dt, steps, stride=1, acc_unit=ACC_KCAL_MOL_A_AMU_FS, forces=False,
+           launches=None) -> dict:
+        """Velocity-Verlet trajectories of Q independent replicas on the device (`mlff_md_run`,
+        csrc/kernels_md.hip): positions R0 (the shapes `predict` accepts), velocities V0 ((Q, 3n),
+        (Q, n, 3), or one geometry's (3n,) / (n, 3)) in [R] per time unit, masses (n,), `steps`
+        steps of dt.  `acc_unit` converts [E] / [R] / mass into [R] / time^2 (the default: kcal/mol,
+        Angstrom, amu, fs).  With h_i = (0.5 dt acc_unit) / m_i a step is
+            v += h_i F;  R += dt v;  E, F = predict(R);  v += h_i F,
+        every product rounded before its sum, so the frames equal those of that loop over
+        `predict` bit for bit; a replica's bits do not depend on the batch, the stride, a restart
+        from a frame, or the device split.  Returns the frames of the steps 0, stride, ..., steps
+        (T = steps / stride + 1): {"R": (Q, T, n, 3), "V": (Q, T, n, 3), "E": (Q, T), "step": (T,)}
+        and "F": (Q, T, 3n) with `forces`; a frame holds R, V, E(R) and F(R) of one instant.
+        Between flushes of the device's frame buffer nothing is copied and nothing waits.
+        launches: 2 or 4 kernel launches per step instead of the model's default (2 needs a tile
+        model); the same bits."""
+        if not self._engines:
+            raise RuntimeError("GDMLPredict is closed")
+        R, V, m, dt, steps, stride = normalize_md_inputs(R0, V0, masses, dt, steps, stride, self.n_atoms)
+        if launches not in (None, 0, 2, 4):
+            raise ValueError(f"launches must be 2 or 4, got {launches!r}")
+        h = (0.5 * dt * acc_unit) / m
+        Q, n = R.shape[0], self.n_atoms
+        T = steps // stride + 1
+
+        def run(eng, a, b):
+            eng.md_set_form(launches or 0)
+            return eng.md_run(R[a:b], V[a:b], h, dt, steps, stride, forces)
+
+        if self._workers is None:
+            parts = [run(self._engines[0], 0, Q)]
+        else:
+            blocks = split_blocks(Q, len(self._engines))
+            parts = self._all(lambda r: run(self._engines[r], *blocks[r]))
+        out = {"R": np.concatenate([p[0] for p in parts]).reshape(Q, T, n, 3),
+               "V": np.concatenate([p[1] for p in parts]).reshape(Q, T, n, 3),
+               "E": np.concatenate([p[2] for p in parts]),
+               "step": np.arange(T, dtype=np.int64) * stride}
+        if forces:
+            out["F"] = np.concatenate([p[3] for p in parts])
+        return out
+
+    def md_info(self) -> tuple[int, int, int]:
+        """(kernel launches per step, frames the device's frame buffer holds, stream
+        synchronisations of the last `md` on the first device: one per flush of that buffer)."""
+        if not self._engines:
+            raise RuntimeError("GDMLPredict is closed")
+        if self._workers is None:
+            return self._engines[0].md_info()
+        return self._all(lambda r: self._engines[r].md_info())[0]
 
     def close(self):
         """Release the device contexts and stop the workers (idempotent)."""

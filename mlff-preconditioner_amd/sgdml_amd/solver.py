@@ -275,6 +275,49 @@ class KernelSolver:
         self._call("mlff_predict_hvp_info", ctypes.byref(fl), ctypes.byref(by))
         return fl.value, by.value
 
+    # ------------------------------------------------------ molecular dynamics
+    def md_run(self, R: np.ndarray, V: np.ndarray, h: np.ndarray, dt: float, n_steps: int,
+               stride: int = 1, forces: bool = False):
+        """`n_steps` velocity-Verlet steps of the Q replicas R (Q x n_atoms x 3) with velocities V
+        (Q x 3 n_atoms) on the device, with the model set by `predict_set_model` (mlff_md_run,
+        csrc/kernels_md.hip): v += h_i F; R += dt v; F at R; v += h_i F, h (n_atoms) = (dt
+        acc_unit / 2) / m_i.  Returns (R, V, E, F) of the T = n_steps / stride + 1 recorded
+        frames: (Q, T, 3n), (Q, T, 3n), (Q, T) and (Q, T, 3n) or None without `forces`."""
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        V = np.ascontiguousarray(V, dtype=np.float64)
+        h = np.ascontiguousarray(h, dtype=np.float64)
+        n = getattr(self, "_pred_n_atoms", None)
+        if n is not None and (R.ndim != 3 or R.shape[1:] != (n, 3)):
+            raise ValueError(f"R must be Q x {n} x 3, got {R.shape}")
+        if n is None and (R.ndim != 3 or R.shape[2] != 3):
+            raise ValueError("R must be Q x n_atoms x 3")
+        Q, n = R.shape[0], R.shape[1]
+        if V.shape != (Q, 3 * n):
+            raise ValueError(f"V must be {Q} x {3 * n}, got {V.shape}")
+        if h.shape != (n,):
+            raise ValueError(f"h must have shape ({n},), got {h.shape}")
+        n_steps, stride = int(n_steps), int(stride)
+        if n_steps < 0 or stride < 1 or n_steps % stride != 0:
+            raise ValueError(f"n_steps must be >= 0 and a multiple of stride >= 1, got {n_steps}, {stride}")
+        T = n_steps // stride + 1
+        Ro, Vo, Eo = np.empty((Q, T, 3 * n)), np.empty((Q, T, 3 * n)), np.empty((Q, T))
+        Fo = np.empty((Q, T, 3 * n)) if forces else None
+        self._call("mlff_md_run", nat.dptr(R), nat.dptr(V), nat.dptr(h), int(Q), float(dt), n_steps,
+                   stride, int(bool(forces)), nat.dptr(Ro), nat.dptr(Vo), nat.dptr(Eo), nat.dptr(Fo))
+        return Ro, Vo, Eo, Fo
+
+    def md_info(self) -> tuple[int, int, int]:
+        """(kernel launches per step, frames the device buffer holds, stream synchronisations of
+        the last `md_run`: one per flush of that buffer) (mlff_md_info)."""
+        launches, cap, syncs = ctypes.c_int(), ctypes.c_int64(), ctypes.c_int64()
+        self._call("mlff_md_info", ctypes.byref(launches), ctypes.byref(cap), ctypes.byref(syncs))
+        return launches.value, cap.value, syncs.value
+
+    def md_set_form(self, launches: int = 0):
+        """The form of `md_run`'s step: 4 launches (any model), 2 (tile models) or 0, the
+        default; the same bits either way (mlff_md_set_form)."""
+        self._call("mlff_md_set_form", int(launches))
+
     def set_operator(self, sigma_K: float, lam: float):
         self._call("mlff_set_operator", float(sigma_K), float(lam))
 
